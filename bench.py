@@ -16,6 +16,12 @@ processes itself (child processes, before any HIP call) and waits for them.
 
 Times exactly K optimizer steps between barrier + device synchronisation on both sides, takes
 the max over ranks, rank 0 prints one JSON line.
+
+A plain run does only that: set up, W warm-up steps, K timed steps, the result line.  Anything
+else the benchmark measures or checks belongs behind `--full` (off by default; nothing lives there
+yet).  `--dump-outputs DIR` writes what the last timed step handed back to its caller (rank 0's
+view) as DIR/<name>.npy after the timed region, see `_dump_outputs`; tokens and initial weights are
+seeded, so with the same arguments two builds of the project can be compared output for output.
 """
 
 from __future__ import annotations
@@ -77,7 +83,16 @@ def parse():
     ap.add_argument("--gloo-gpu", action="store_true",
                     help="test mode: every rank on cuda:0 with gloo collectives on staged GPU tensors (multi-rank "
                          "rehearsal of the GPU code path on a one-GPU box; not a measurement)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline figure (none so far: a plain "
+                         "run and a --full run do the same work)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs (loss, gradient norm, seeded "
+                         "samples of the updated weights) to DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def _free_port() -> int:
@@ -448,6 +463,53 @@ def _check_initial_loss(loss, cfg, dev) -> float:
     return v
 
 
+DUMP_SEED = 97531
+DUMP_PER_PARAM = 8192        # sampled elements per model parameter
+DUMP_PER_MASTER = 1 << 20    # sampled elements per flat fp32 master buffer
+DUMP_MAX_ELEMS = 4 << 20     # cap per file (16 MB of float32): three sampled files stay far below 64 MB
+
+
+def _dump_outputs(out_dir: str, loss, model, opt) -> None:
+    """--dump-outputs: what the last timed step handed back to its caller, as `out_dir`/<name>.npy.
+
+      loss.npy       float64 [1]  the step's loss (mean over its micro-batches)
+      grad_norm.npy  float64 [1]  the global gradient norm the step clipped with (when the optimizer has one)
+      params.npy     float32      the updated model weights: up to DUMP_PER_PARAM elements of every
+                                  parameter of this rank, in `named_parameters()` order
+      master.npy     float32      the updated fp32 master weights: up to DUMP_PER_MASTER elements of
+                                  every flat buffer of this rank's optimizer (when it keeps them)
+
+    Whole tensors below the sample size, otherwise elements at indices drawn from one generator
+    seeded with DUMP_SEED: the same indices for the same model in every run and build."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+
+    def sample(tensors, per):
+        per = max(1, min(per, DUMP_MAX_ELEMS // max(1, len(tensors))))
+        parts = []
+        for t in tensors:
+            flat = t.detach().reshape(-1)
+            if flat.numel() > per:
+                flat = flat[torch.randint(0, flat.numel(), (per,), generator=g).to(flat.device)]
+            parts.append(flat.float().cpu())
+        return torch.cat(parts).numpy() if parts else np.zeros(0, dtype=np.float32)
+
+    def scalar(v):
+        return np.array([float(v.item() if torch.is_tensor(v) else v)], dtype=np.float64)
+
+    np.save(os.path.join(out_dir, "loss.npy"), scalar(loss))
+    grad_norm = getattr(opt, "grad_norm", None)
+    if grad_norm is not None:
+        np.save(os.path.join(out_dir, "grad_norm.npy"), scalar(grad_norm))
+    np.save(os.path.join(out_dir, "params.npy"), sample([p for _, p in model.named_parameters()], DUMP_PER_PARAM))
+    masters = [b.master for b in getattr(getattr(opt, "optimizer", opt), "buffers", []) if hasattr(b, "master")]
+    if masters:
+        np.save(os.path.join(out_dir, "master.npy"), sample(masters, DUMP_PER_MASTER))
+
+
 def main(a):
     import torch
     import torch.distributed as dist
@@ -594,7 +656,7 @@ def main(a):
     tokens = a.gbs * a.seq * a.steps
     value = tokens / el
     if rank == 0:
-        mem = torch.cuda.max_memory_allocated(dev) / 2**30 if use_cuda else 0.0
+        mem =torch.cuda.max_memory_allocated(dev) / 2**30 if use_cuda else 0.0
         nparams = llama_num_params(cfg)
         fpt = model_flops_per_token(nparams, cfg.num_hidden_layers, cfg.hidden_size, a.seq)
         par = f"tp{tp}" + ("_sp" if over["sequence_parallel_enabled"] else "") + \
@@ -635,6 +697,8 @@ def main(a):
             "sp_streams": stream_split.parts() if (over["sequence_parallel_enabled"] or stream_split.without_sp()) else 1,
             "api": "nxd.initialize_parallel_model / initialize_parallel_optimizer",
         }
+        if a.dump_outputs:
+            _dump_outputs(a.dump_outputs, loss, model, opt)
         print(json.dumps(rec), flush=True)
     if watchdog is not None:
         watchdog.stop()

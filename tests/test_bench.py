@@ -45,6 +45,35 @@ def test_bench_self_spawn(n):
     _check(recs[0], n)
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float32 / float64 .npy files below the
+    64 MB cap; the inputs are seeded, so a second run (here with --full, which adds nothing to the
+    result line's headline keys) reproduces them; --steps sets the number of timed steps."""
+    import numpy as np
+
+    dumps = []
+    for i, extra in enumerate(([], ["--full"])):
+        d = tmp_path / f"run{i}"
+        args = [*ARGS, "--steps", "2"]    # the later --steps wins
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", *args, "--dump-outputs", str(d), *extra],
+                           cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        recs = _json_lines(r.stdout)
+        assert len(recs) == 1, r.stdout
+        assert recs[0]["steps"] == 2 and recs[0]["ms_per_step"] > 0
+        files = sorted(os.listdir(d))
+        assert {"loss.npy", "params.npy"} <= set(files) and all(f.endswith(".npy") for f in files), files
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in arrs.values())
+        assert sum(v.nbytes for v in arrs.values()) <= 64 * 2**20
+        assert abs(float(arrs["loss.npy"][0]) - recs[0]["loss"]) < 1e-3
+        assert arrs["params.npy"].size > 1000 and arrs["master.npy"].shape[0] > 1000
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        np.testing.assert_allclose(dumps[0][f], dumps[1][f], rtol=1e-5, atol=1e-7, err_msg=f)
+
+
 def test_bench_torchrun():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29631", "bench.py", "--gpus", "2", *ARGS],
