@@ -73,6 +73,10 @@ def parse(argv=None):
     p.add_argument("--expert_parallel_size", type=int, default=1)
     p.add_argument("--capacity_factor", type=float, default=None, help="MoE: None = dropless (full capacity)")
     p.add_argument("--moe_router", default="topk", choices=["topk", "sinkhorn"])
+    p.add_argument("--document-masking-eos-id", type=int, default=None,
+                   help="llama: attention does not cross the documents of a packed row (a document ends with this token id)")
+    p.add_argument("--reset-position-ids", action="store_true",
+                   help="llama, with --document-masking-eos-id: rotary positions restart at every document")
     return p.parse_args(argv)
 
 
@@ -110,6 +114,12 @@ def model_config(a):
     cfg.selective_checkpoint_enabled = a.selective_checkpoint_enabled
     cfg.kv_shared_group_size = a.kv_replicator
     cfg.max_position_embeddings = max(cfg.max_position_embeddings, a.seq_len)
+    # (other example scripts reuse this function with their own parsers, which lack the flag)
+    if getattr(a, "document_masking_eos_id", None) is not None:
+        if a.model_family != "llama":
+            raise SystemExit("--document-masking-eos-id is implemented for --model_family llama only")
+        cfg.document_masking_eos_token_id = a.document_masking_eos_id
+        cfg.reset_position_ids = a.reset_position_ids
     if a.model_family == "mixtral":
         cfg.capacity_factor = a.capacity_factor
         cfg.moe_router = a.moe_router

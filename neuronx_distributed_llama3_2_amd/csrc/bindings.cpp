@@ -16,7 +16,7 @@
 namespace nxd {
 int flash_attn_fwd_launch(const void*, const void*, const void*, void*, float*, const int64_t*, const int64_t*,
                           const int64_t*, const int64_t*, int, int, int, int, int, int, float, int, int,
-                          const DropoutArgs&, hipStream_t);
+                          const DropoutArgs&, const int*, const int*, hipStream_t);
 int64_t flash_attn_bwd_workspace(int, int, int, int, int, int, int, int);
 void flash_attn_bwd_set_knob(int, int);
 int transpose_bf16_launch(const void*, void*, int64_t, int64_t, int64_t, int64_t, hipStream_t);
@@ -24,7 +24,7 @@ void transpose_set_variant(int);
 int flash_attn_bwd_launch(const void*, const void*, const void*, const void*, const void*, const float*, float*,
                           void*, void*, void*, const int64_t*, const int64_t*, const int64_t*, const int64_t*,
                           const int64_t*, const int64_t*, const int64_t*, const int64_t*, int, int, int, int, int, int,
-                          float, int, int, const DropoutArgs&, hipStream_t);
+                          float, int, int, const DropoutArgs&, const int*, const int*, hipStream_t);
 int rmsnorm_fwd_launch(const void*, const void*, const void*, void*, void*, float*, int64_t, int, float, hipStream_t);
 int rmsnorm_bwd_num_partials(int64_t);
 void rmsnorm_set_rows_path(int);
@@ -131,8 +131,20 @@ nxd::DropoutArgs dropout_args(double p, int64_t seed, int64_t head_offset) {
   return d;
 }
 
+// optional interval-mask tensor: int32, contiguous, [B, S], on the device of `like`; nullptr if absent
+const int* range_ptr(const c10::optional<at::Tensor>& t, const char* n, int64_t B, int64_t S, const at::Tensor& like) {
+  if (!t.has_value()) return nullptr;
+  check_cuda(*t, n);
+  TORCH_CHECK(t->device() == like.device(), n, " must be on the device of q");
+  TORCH_CHECK(t->scalar_type() == at::kInt, n, " must be int32");
+  TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == S, n, " must be [", B, ", ", S, "]");
+  TORCH_CHECK(t->is_contiguous(), n, " must be contiguous");
+  return t->data_ptr<int>();
+}
+
 void flash_attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse, double scale, bool causal,
-                    int64_t causal_offset, double dropout_p, int64_t seed, int64_t head_offset) {
+                    int64_t causal_offset, double dropout_p, int64_t seed, int64_t head_offset,
+                    c10::optional<at::Tensor> lo, c10::optional<at::Tensor> hi) {
   int64_t qs[3], ks[3], vs[3], os[3];
   bshd_strides(q, "q", qs);
   bshd_strides(k, "k", ks);
@@ -147,15 +159,20 @@ void flash_attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::
   TORCH_CHECK(Sk > 0, "empty key sequence");
   TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == (int64_t)B * Hq * Sq,
               "lse must be contiguous fp32 [B, Hq, Sq]");
+  TORCH_CHECK(lo.has_value() == hi.has_value(), "lo and hi must be passed together");
+  TORCH_CHECK(!lo.has_value() || dropout_p == 0.0, "interval-masked attention does not support dropout");
+  const int* lo_p = range_ptr(lo, "lo", B, Sq, q);
+  const int* hi_p = range_ptr(hi, "hi", B, Sq, q);
   check_rc(nxd::flash_attn_fwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr<float>(), qs, ks,
                                       vs, os, B, Sq, Sk, Hq, Hkv, D, (float)scale, causal ? 1 : 0, (int)causal_offset,
-                                      dropout_args(dropout_p, seed, head_offset), cur_stream()),
+                                      dropout_args(dropout_p, seed, head_offset), lo_p, hi_p, cur_stream()),
            "flash_attn_fwd");
 }
 
 void flash_attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor dout, at::Tensor lse,
                     at::Tensor dq, at::Tensor dk, at::Tensor dv, double scale, bool causal, int64_t causal_offset,
-                    double dropout_p, int64_t seed, int64_t head_offset) {
+                    double dropout_p, int64_t seed, int64_t head_offset, c10::optional<at::Tensor> lo,
+                    c10::optional<at::Tensor> hi, c10::optional<at::Tensor> q_lo, c10::optional<at::Tensor> q_hi) {
   int64_t qs[3], ks[3], vs[3], os[3], dos[3], dqs[3], dks[3], dvs[3];
   bshd_strides(q, "q", qs);
   bshd_strides(k, "k", ks);
@@ -173,6 +190,14 @@ void flash_attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::
   TORCH_CHECK(D == 64 || D == 128, "head_dim must be 64 or 128");
   TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "num q heads must be a multiple of num kv heads");
   TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == (int64_t)B * Hq * Sq, "bad lse");
+  TORCH_CHECK(lo.has_value() == hi.has_value() && lo.has_value() == q_lo.has_value() && lo.has_value() == q_hi.has_value(),
+              "lo, hi, q_lo and q_hi must be passed together");
+  TORCH_CHECK(!lo.has_value() || dropout_p == 0.0, "interval-masked attention does not support dropout");
+  // the kernel consumes the transposed (per-key) form; the per-query pair is validated with it
+  range_ptr(lo, "lo", B, Sq, q);
+  range_ptr(hi, "hi", B, Sq, q);
+  const int* q_lo_p = range_ptr(q_lo, "q_lo", B, Sk, q);
+  const int* q_hi_p = range_ptr(q_hi, "q_hi", B, Sk, q);
   auto opts = q.options().dtype(at::kFloat);
   // fp32 workspace: dQ / dK / dV accumulators + per-row constants (sized by the kernel TU)
   at::Tensor ws = at::empty({nxd::flash_attn_bwd_workspace(B, Sq, Sk, Hq, Hkv, D, causal ? 1 : 0, (int)causal_offset)}, opts);
@@ -180,7 +205,7 @@ void flash_attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::
                                       lse.data_ptr<float>(), ws.data_ptr<float>(), dq.data_ptr(),
                                       dk.data_ptr(), dv.data_ptr(), qs, ks, vs, os, dos, dqs, dks, dvs, B, Sq, Sk, Hq, Hkv, D,
                                       (float)scale, causal ? 1 : 0, (int)causal_offset,
-                                      dropout_args(dropout_p, seed, head_offset), cur_stream()),
+                                      dropout_args(dropout_p, seed, head_offset), q_lo_p, q_hi_p, cur_stream()),
            "flash_attn_bwd");
 }
 
@@ -1129,10 +1154,11 @@ PYBIND11_MODULE(_C, m) {
   m.doc() = "CDNA4 (gfx950) kernels of neuronx_distributed_llama3_2_amd";
   m.def("flash_attn_fwd", &flash_attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"),
         py::arg("scale"), py::arg("causal"), py::arg("causal_offset"), py::arg("dropout_p") = 0.0, py::arg("seed") = 0,
-        py::arg("head_offset") = 0);
+        py::arg("head_offset") = 0, py::arg("lo") = py::none(), py::arg("hi") = py::none());
   m.def("flash_attn_bwd", &flash_attn_bwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"),
         py::arg("lse"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("scale"), py::arg("causal"),
-        py::arg("causal_offset"), py::arg("dropout_p") = 0.0, py::arg("seed") = 0, py::arg("head_offset") = 0);
+        py::arg("causal_offset"), py::arg("dropout_p") = 0.0, py::arg("seed") = 0, py::arg("head_offset") = 0,
+        py::arg("lo") = py::none(), py::arg("hi") = py::none(), py::arg("q_lo") = py::none(), py::arg("q_hi") = py::none());
   // A/B knobs of the backward: 0 = ablation flags, 1 = chunk override (0 = auto)
   m.def("flash_attn_set_knob", [](int which, int value) { nxd::flash_attn_bwd_set_knob(which, value); });
   m.def("rmsnorm_fwd", &rmsnorm_fwd);

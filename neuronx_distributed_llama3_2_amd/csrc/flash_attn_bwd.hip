@@ -75,6 +75,11 @@ struct BwdParams {
                // 2 no dK/dV atomics, 16 no Q/dO tile loads,
                // 32 no per-tile barriers
   DropoutArgs drop;  // DROP variants only
+  // RANGE variants only: key k of batch row b is seen by the queries [rq_lo[b, k], rq_hi[b, k])
+  // (int32 [B, Sk], each non-decreasing along k: the transposed form of the forward's per-query
+  // key intervals), intersected with the causal limit
+  const int* rq_lo;
+  const int* rq_hi;
 };
 
 // (q head x q tile) iterations of key block kb
@@ -147,7 +152,11 @@ __device__ __forceinline__ void mfma_acc_agpr(f32x16_t& acc, const TA& a, const 
 // DROP: attention dropout (reference NKI flash_attn_bwd dropout_p / seed): the forward's keep mask m
 // (0 or 1/(1-p)) is regenerated from the hash; dV uses P*m, dS = P * (m * dO.V^T - delta), so dP
 // starts at 0 instead of -delta and delta is re-read from the tile's LDS row constants.
-template <int D, int PIPE, int PIPE_DVDK, bool DROP>
+// RANGE: per-key query intervals.  The item count per key block stays the shape-only kb_iters plan
+// (host plan, workspace and slab layout untouched); inside the kernel the block's query tiles are
+// restricted to [q_lo of its first key, q_hi of its last key) and that smaller (q head x q tile)
+// space is split over the same items -- items left with nothing take the empty-item path.
+template <int D, int PIPE, int PIPE_DVDK, bool DROP, bool RANGE = false>
 __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
   constexpr int kPipe = PIPE;
   constexpr int CH = D / 8;
@@ -182,13 +191,26 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
   // ---- decode (key block, chunk) of this work item: key blocks in order (heaviest first)
   const int nkb = (p.Sk + kBlockK - 1) / kBlockK;
   int kb = 0, it_begin = 0, it_end = 0;
+  int r_qstart = 0, r_nqt = 0;  // RANGE: the block's restricted first query row / query tiles
   for (; kb < nkb; ++kb) {
     const int n_it = kb_iters(kb, p.Sq, G, p.causal, p.causal_offset);
     const int nc = (n_it + p.chunk - 1) / p.chunk;
     if (kc < nc) {
-      const int per = (n_it + nc - 1) / nc;
+      int n_work = n_it;
+      if constexpr (RANGE) {
+        // the queries that see any key of this block: [q_lo[first key], q_hi[last key]) (both are
+        // non-decreasing along the key), cut to whole tiles inside the causal range
+        const int64_t krow = (int64_t)(bh / p.Hkv) * p.Sk;
+        const int cq = p.causal ? max(0, kb * kBlockK - p.causal_offset) : 0;
+        const int qa = max(cq, min(max(p.rq_lo[krow + kb * kBlockK], 0), p.Sq));
+        const int qe = min(max(p.rq_hi[krow + min(kb * kBlockK + kBlockK, p.Sk) - 1], 0), p.Sq);
+        r_qstart = (qa / kBlockQ) * kBlockQ;
+        r_nqt = qe > r_qstart ? (qe - r_qstart + kBlockQ - 1) / kBlockQ : 0;
+        n_work = G * r_nqt;
+      }
+      const int per = (n_work + nc - 1) / nc;
       it_begin = kc * per;
-      it_end = min(n_it, it_begin + per);
+      it_end = min(n_work, it_begin + per);
       break;
     }
     kc -= nc;
@@ -209,7 +231,8 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
   int qstart = 0;
   if (p.causal) qstart = max(0, kb * kBlockK - p.causal_offset);
   qstart = (qstart / kBlockQ) * kBlockQ;
-  const int n_qt = (p.Sq - qstart + kBlockQ - 1) / kBlockQ;
+  if constexpr (RANGE) qstart = r_qstart;
+  const int n_qt = RANGE ? r_nqt : (p.Sq - qstart + kBlockQ - 1) / kBlockQ;
 
   // (w stays a VGPR value: made scalar, its uniform branches split the tile body into blocks and
   // the allocator spills the V rows)
@@ -221,6 +244,22 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
   const uint16_t* vbase = p.v + (int64_t)b * p.v_sb + (int64_t)hkv * p.v_sh;
   const int kb0 = kb * kBlockK;
   const int wkey0 = kb0 + 64 * w;  // this wave's first key
+
+  // RANGE: the query interval of this lane's two keys, loaded once per work item, and per 32-key
+  // column the wave-uniform bounds inside which a query tile needs no range mask (the column's
+  // first key has its smallest q_hi, its last key its largest q_lo)
+  int my_q_lo[2] = {0, 0}, my_q_hi[2] = {0, 0};
+  int col_q_lo[2] = {0, 0}, col_q_hi[2] = {0, 0};
+  if constexpr (RANGE) {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int64_t ki = (int64_t)b * p.Sk + min(wkey0 + 32 * c + r, p.Sk - 1);  // keys >= Sk are masked anyway
+      my_q_lo[c] = p.rq_lo[ki];
+      my_q_hi[c] = p.rq_hi[ki];
+      col_q_lo[c] = __builtin_amdgcn_readlane(my_q_lo[c], 31);
+      col_q_hi[c] = __builtin_amdgcn_readlane(my_q_hi[c], 0);
+    }
+  }
 
   // ---- K block -> LDS; this wave's V rows -> registers (B operands of dP)
   for (int idx = tid; idx < kBlockK * CH; idx += kThreads) {
@@ -440,7 +479,8 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
         __builtin_amdgcn_sched_barrier(0);
         // ---- P, dS (element e of the lane: query row 8(e>>2) + 4hh + (e&3), key kc0 + r).  Rows
         // 0-15 (half 0) first; the exps of half 1 run in the shadow of half 0's dV / dK MFMAs.
-        const bool need_mask = (p.causal && kc0 + 31 > qt0 + p.causal_offset) || qt0 + kBlockQ > p.Sq || kc0 + 32 > p.Sk;
+        bool need_mask = (p.causal && kc0 + 31 > qt0 + p.causal_offset) || qt0 + kBlockQ > p.Sq || kc0 + 32 > p.Sk;
+        if constexpr (RANGE) need_mask = need_mask || qt0 < col_q_lo[c] || qt0 + kBlockQ > col_q_hi[c];
         float pv[16];
         bf16x8_t pf[2], dsf[2];
         auto p_fix = [&](int e0) {  // masked tiles only (a VALU-only exec-masked block)
@@ -448,7 +488,8 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
 #pragma unroll
           for (int e = e0; e < e0 + 8; ++e) {
             const int qg = qt0 + 8 * (e >> 2) + 4 * hh + (e & 3);
-            const bool bad = qg >= p.Sq || my_key >= p.Sk || (p.causal && my_key > qg + p.causal_offset);
+            bool bad = qg >= p.Sq || my_key >= p.Sk || (p.causal && my_key > qg + p.causal_offset);
+            if constexpr (RANGE) bad = bad || qg < my_q_lo[c] || qg >= my_q_hi[c];
             pv[e] = bad ? 0.f : pv[e];
           }
         };
@@ -862,15 +903,15 @@ int pipe_variant() {
   return g_pipe;
 }
 
-template <int D, int PIPE, int PIPE_DVDK, bool DROP = false>
+template <int D, int PIPE, int PIPE_DVDK, bool DROP = false, bool RANGE = false>
 void launch_bwd(const BwdParams& p, int64_t items, size_t lds, hipStream_t stream) {
   static bool attr_set = false;  // > 64 KiB of dynamic LDS must be opted into once per instantiation
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)bwd_kernel<D, PIPE, PIPE_DVDK, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)bwd_kernel<D, PIPE, PIPE_DVDK, DROP, RANGE>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
     attr_set = true;
   }
-  hipLaunchKernelGGL((bwd_kernel<D, PIPE, PIPE_DVDK, DROP>), dim3((unsigned)items), dim3(kThreads), lds, stream, p);
+  hipLaunchKernelGGL((bwd_kernel<D, PIPE, PIPE_DVDK, DROP, RANGE>), dim3((unsigned)items), dim3(kThreads), lds, stream, p);
 }
 
 }  // namespace fab
@@ -916,9 +957,12 @@ int flash_attn_bwd_launch(const void* q, const void* k, const void* v, const voi
                           const int64_t* qs, const int64_t* ks, const int64_t* vs, const int64_t* os,
                           const int64_t* dos, const int64_t* dqs, const int64_t* dks, const int64_t* dvs,
                           int B, int Sq, int Sk, int Hq, int Hkv, int D, float softmax_scale, int causal,
-                          int causal_offset, const DropoutArgs& drop, hipStream_t stream) {
+                          int causal_offset, const DropoutArgs& drop, const int* range_q_lo, const int* range_q_hi,
+                          hipStream_t stream) {
   using namespace fab;
   if (Hkv <= 0 || Hq % Hkv != 0 || (D != 64 && D != 128)) return -1;
+  const bool range = range_q_lo != nullptr;
+  if (range && (range_q_hi == nullptr || drop.enabled())) return -3;  // no RANGE + DROP instantiation
   const int G = Hq / Hkv;
   const int64_t Sq_pad = (Sq + kBlockQ - 1) / kBlockQ * kBlockQ;
   const int nkb = (Sk + kBlockK - 1) / kBlockK;
@@ -979,10 +1023,14 @@ int flash_attn_bwd_launch(const void* q, const void* k, const void* v, const voi
   p.ablate = ablate_flags();
   p.xcd_map = xcd_map_mode();
   p.drop = drop;
+  p.rq_lo = range_q_lo;
+  p.rq_hi = range_q_hi;
   if (items > 0) {
     if (D == 128) {
       const size_t lds = kBlockK * 128 * 2 + 4 * kBlockQ * 128 * 2 + kBlockK * 64 + 512 + 128 * 128 * 2;
-      if (drop.enabled()) {
+      if (range) {
+        launch_bwd<128, 1, 2, false, true>(p, items, lds, stream);
+      } else if (drop.enabled()) {
         launch_bwd<128, 1, 2, true>(p, items, lds, stream);
       } else switch (pipe_variant()) {
         case 11: launch_bwd<128, 1, 1>(p, items, lds, stream); break;
@@ -992,7 +1040,9 @@ int flash_attn_bwd_launch(const void* q, const void* k, const void* v, const voi
       }
     } else {
       const size_t lds = kBlockK * 64 * 2 + 4 * kBlockQ * 64 * 2 + kBlockK * 64 + 512 + 2 * 64 * 16 * 4 + 128 * 64 * 2;
-      if (drop.enabled())
+      if (range)
+        launch_bwd<64, 1, 2, false, true>(p, items, lds, stream);
+      else if (drop.enabled())
         launch_bwd<64, 1, 2, true>(p, items, lds, stream);
       else
         launch_bwd<64, 1, 2>(p, items, lds, stream);

@@ -47,6 +47,10 @@ struct FwdParams {
   int causal;
   int causal_offset;  // query i attends keys <= i + causal_offset (Sk - Sq for bottom-right alignment)
   DropoutArgs drop;   // DROP variants only
+  // RANGE variants only: query i of batch row b sees keys [rlo[b, i], rhi[b, i]) (int32 [B, Sq], each
+  // non-decreasing along i), intersected with the causal limit
+  const int* rlo;
+  const int* rhi;
 };
 
 // 16-byte chunk swizzle of a [rows][D] bf16 LDS image (D/8 chunks per row).
@@ -102,7 +106,11 @@ __device__ __forceinline__ float xor32(float x, bool is_max) {
 // DROP: dropout on the probabilities (reference NKI flash_fwd dropout_p / seed): the row sum l and
 // the LSE use the undropped P, the P.V operand is P * keep / (1 - p); the lane's query row hash is
 // computed once, each score costs one more hash.
-template <int D, int W, bool DROP>
+// RANGE: per-query key intervals (packed documents, right padding, sliding windows).  lo / hi are
+// non-decreasing along the query, so the workgroup's (wave's) first row has the smallest lo and its
+// last row the largest hi: the tile loop runs only over the tiles between them, a wave skips the
+// tiles none of its rows sees, and the mask is applied only on tiles some row sees partially.
+template <int D, int W, bool DROP, bool RANGE = false>
 __global__ void __launch_bounds__(W * 64, 8 / W) fwd_kernel(FwdParams p) {
   constexpr int kWaves = W;
   constexpr int kBlockM = W * 32;                 // q rows per workgroup
@@ -150,7 +158,25 @@ __global__ void __launch_bounds__(W * 64, 8 / W) fwd_kernel(FwdParams p) {
   // ---- key range
   int kend = p.Sk;
   if (p.causal) kend = min(p.Sk, qb0 + kBlockM + p.causal_offset);
-  const int ntiles = kend > 0 ? (kend + kBlockN - 1) / kBlockN : 0;
+  int tstart = 0;                       // first key tile (RANGE: the block's first row's lo)
+  int my_lo = 0, my_hi = 0;             // RANGE: this lane's row interval, clamped to [0, Sk]
+  int wave_lo = 0, wave_lo_max = 0, wave_hi = 0, wave_hi_min = 0;  // RANGE: over the wave's rows
+  if constexpr (RANGE) {
+    const int* rlo = p.rlo + (int64_t)b * p.Sq;
+    const int* rhi = p.rhi + (int64_t)b * p.Sq;
+    const int qlast = min(qb0 + kBlockM, p.Sq) - 1;
+    kend = min(kend, min(rhi[qlast], p.Sk));
+    tstart = min(max(rlo[qb0], 0), p.Sk) / kBlockN;
+    const int qi = min(my_q, p.Sq - 1);  // rows past the end repeat the last row (never stored)
+    my_lo = min(max(rlo[qi], 0), p.Sk);
+    my_hi = min(max(rhi[qi], 0), p.Sk);
+    wave_lo = __builtin_amdgcn_readlane(my_lo, 0);
+    wave_lo_max = __builtin_amdgcn_readlane(my_lo, 31);
+    wave_hi_min = __builtin_amdgcn_readlane(my_hi, 0);
+    wave_hi = __builtin_amdgcn_readlane(my_hi, 31);
+  }
+  // one past the last key tile (tiles [tstart, ntiles); tstart is 0 without RANGE)
+  const int ntiles = kend > tstart * kBlockN ? (kend + kBlockN - 1) / kBlockN : 0;
   const int wave_qmax = q0 + 31 + p.causal_offset;  // last key any row of this wave may see
   const int wave_qmin = q0 + p.causal_offset;
 
@@ -186,7 +212,7 @@ __global__ void __launch_bounds__(W * 64, 8 / W) fwd_kernel(FwdParams p) {
     }
   };
 
-  if (ntiles > 0) issue_tile(0, 0);
+  if (ntiles > 0) issue_tile(tstart, 0);
   // static priority for the younger half of an 8-wave workgroup (MI355X_MICROARCH "Two waves per
   // SIMD" item 4); the condition is wave-uniform through readfirstlane (T5 static form)
   if (kWaves == 8 && __builtin_amdgcn_readfirstlane(w) >= kWaves / 2) __builtin_amdgcn_s_setprio(1);
@@ -223,7 +249,8 @@ __global__ void __launch_bounds__(W * 64, 8 / W) fwd_kernel(FwdParams p) {
 
     {
       const int kt0 = t * kBlockN;
-      const bool wave_active = kt0 <= wave_qmax || !p.causal;
+      bool wave_active = kt0 <= wave_qmax || !p.causal;
+      if constexpr (RANGE) wave_active = wave_active && kt0 < wave_hi && kt0 + kBlockN > wave_lo;
       if (wave_active) {
         const char* kl = smem + buf * 2 * TILE_BYTES;
         // ---- S^T for the two 32-key subtiles
@@ -263,19 +290,25 @@ __global__ void __launch_bounds__(W * 64, 8 / W) fwd_kernel(FwdParams p) {
         issue(std::integral_constant<int, 1>{}, vb2);
         // ---- mask + tile max on the RAW scores (scale > 0 commutes with max); the scale is folded
         // into one FMA per score below: p = exp2(s * c - m*c)
-        const bool need_mask = (kt0 + kBlockN > p.Sk) || (p.causal && kt0 + kBlockN - 1 > wave_qmin);
+        bool need_mask = (kt0 + kBlockN > p.Sk) || (p.causal && kt0 + kBlockN - 1 > wave_qmin);
+        if constexpr (RANGE) need_mask = need_mask || kt0 < wave_lo_max || kt0 + kBlockN > wave_hi_min;
         float tmax = -INFINITY;
         {
           // branch-free select against one per-lane limit: key offset c inside the tile is masked
           // iff c > lim (one compare + select per score, only on tiles that need a mask)
           if (need_mask) {
-            const int lim = (p.causal ? min(my_q + p.causal_offset, p.Sk - 1) : p.Sk - 1) - kt0 - 4 * hh;
+            int lim = (p.causal ? min(my_q + p.causal_offset, p.Sk - 1) : p.Sk - 1) - kt0 - 4 * hh;
+            if constexpr (RANGE) lim = min(lim, my_hi - 1 - kt0 - 4 * hh);
+            const int lim_lo = my_lo - kt0 - 4 * hh;  // RANGE: offsets below it are masked too
   #pragma unroll
             for (int j = 0; j < 2; ++j)
   #pragma unroll
               for (int e = 0; e < 16; ++e) {
                 const int c = 32 * j + (e & 3) + 8 * (e >> 2);
-                sacc[j][e] = c > lim ? -INFINITY : sacc[j][e];
+                if constexpr (RANGE)
+                  sacc[j][e] = (c > lim || c < lim_lo) ? -INFINITY : sacc[j][e];
+                else
+                  sacc[j][e] = c > lim ? -INFINITY : sacc[j][e];
               }
           }
   #pragma unroll
@@ -345,7 +378,8 @@ __global__ void __launch_bounds__(W * 64, 8 / W) fwd_kernel(FwdParams p) {
     }
     __syncthreads();  // vmcnt(0) + barrier: tile t+1 has landed for every wave
   };
-  for (int t = 0; t < ntiles; t += 2) {
+  // (the first tile is in buffer 0 whatever its number)
+  for (int t = tstart; t < ntiles; t += 2) {
     tile(t, std::integral_constant<int, 0>{});
     if (t + 1 < ntiles) tile(t + 1, std::integral_constant<int, 1>{});
   }
@@ -377,7 +411,8 @@ __global__ void __launch_bounds__(W * 64, 8 / W) fwd_kernel(FwdParams p) {
 int flash_attn_fwd_launch(const void* q, const void* k, const void* v, void* o, float* lse,
                           const int64_t* qs, const int64_t* ks, const int64_t* vs, const int64_t* os,
                           int B, int Sq, int Sk, int Hq, int Hkv, int D, float softmax_scale,
-                          int causal, int causal_offset, const DropoutArgs& drop, hipStream_t stream) {
+                          int causal, int causal_offset, const DropoutArgs& drop, const int* range_lo,
+                          const int* range_hi, hipStream_t stream) {
   using namespace fa;
   FwdParams p{};
   p.q = (const uint16_t*)q;
@@ -394,6 +429,10 @@ int flash_attn_fwd_launch(const void* q, const void* k, const void* v, void* o, 
   p.causal = causal;
   p.causal_offset = causal_offset;
   p.drop = drop;
+  p.rlo = range_lo;
+  p.rhi = range_hi;
+  const bool range = range_lo != nullptr;
+  if (range && (range_hi == nullptr || drop.enabled())) return -3;  // no RANGE + DROP instantiation
   if (Hkv <= 0 || Hq % Hkv != 0) return -1;
   if (D != 128 && D != 64) return -2;
   // 8-wave workgroups (256 query rows: half the K/V tile traffic and barriers per row) while the
@@ -406,8 +445,15 @@ int flash_attn_fwd_launch(const void* q, const void* k, const void* v, void* o, 
   const int grid = ((Sq + rows - 1) / rows) * B * Hq;
   if (grid == 0) return 0;
   const size_t lds = 2 * 2 * kBlockN * D * 2;
-#define NXD_FA_LAUNCH(DD, WW, DR) hipLaunchKernelGGL((fwd_kernel<DD, WW, DR>), dim3(grid), dim3(WW * 64), lds, stream, p)
-  if (drop.enabled()) {
+#define NXD_FA_LAUNCH(DD, WW, DR, ...) \
+  hipLaunchKernelGGL((fwd_kernel<DD, WW, DR, ##__VA_ARGS__>), dim3(grid), dim3(WW * 64), lds, stream, p)
+  if (range) {
+    if (D == 128) {
+      if (w8) NXD_FA_LAUNCH(128, 8, false, true); else NXD_FA_LAUNCH(128, 4, false, true);
+    } else {
+      if (w8) NXD_FA_LAUNCH(64, 8, false, true); else NXD_FA_LAUNCH(64, 4, false, true);
+    }
+  } else if (drop.enabled()) {
     if (D == 128) {
       if (w8) NXD_FA_LAUNCH(128, 8, true); else NXD_FA_LAUNCH(128, 4, true);
     } else {

@@ -40,23 +40,27 @@ def _dropout_attn(q, k, v, causal, softmax_scale, layout, dropout_p, seed):
 
 def flash_attn_func(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
                     softmax_scale: Optional[float] = None, layout: str = "bhsd", dropout_p: float = 0.0,
-                    seed: Optional[int] = None) -> torch.Tensor:
+                    seed: Optional[int] = None, key_ranges=None) -> torch.Tensor:
+    """key_ranges: optional interval mask (ops/attention_ranges.py); not with dropout."""
     if dropout_p:
+        if key_ranges is not None:
+            raise ValueError("key_ranges cannot be combined with attention dropout")
         return _dropout_attn(q, k, v, causal, softmax_scale, layout, dropout_p, seed)
     if layout == "bshd":
-        return _fa(q, k, v, causal=causal, softmax_scale=softmax_scale)
+        return _fa(q, k, v, causal=causal, softmax_scale=softmax_scale, key_ranges=key_ranges)
     if layout == "bhsd":
-        o = _fa(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal=causal, softmax_scale=softmax_scale)
+        o = _fa(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal=causal, softmax_scale=softmax_scale,
+                key_ranges=key_ranges)
         return o.transpose(1, 2)
     if layout == "nki":
         o = _fa(q.permute(0, 3, 1, 2), k.permute(0, 3, 1, 2), v.transpose(1, 2), causal=causal,
-                softmax_scale=softmax_scale)
+                softmax_scale=softmax_scale, key_ranges=key_ranges)
         return o.transpose(1, 2)  # [B, H, S, D]
     raise ValueError(f"unknown layout {layout}")
 
 
 def nki_flash_attn_func(query, key, value, droupout_p: float = 0.0, softmax_scale: Optional[float] = None,
-                        causal: bool = True, seed: Optional[int] = None):
+                        causal: bool = True, seed: Optional[int] = None, key_ranges=None):
     """Reference-named alias: query/key [B, H, D, S], value [B, H, S, D] -> [B, H, S, D]."""
     return flash_attn_func(query, key, value, causal=causal, softmax_scale=softmax_scale, layout="nki",
-                           dropout_p=droupout_p, seed=seed)
+                           dropout_p=droupout_p, seed=seed, key_ranges=key_ranges)

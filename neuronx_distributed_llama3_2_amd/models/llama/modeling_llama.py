@@ -113,11 +113,13 @@ class LlamaAttention(nn.Module):
             _regroup_row_parallel(self.o_proj, tp, kv_mult)
         self.rope_cache = rope_cache
 
-    def forward(self, x):
+    def forward(self, x, key_ranges=None, positions=None):
+        """key_ranges: interval mask of the packed documents (ops.KeyRanges); positions: int [B, S]
+        rotary positions.  Both None: plain causal attention at positions 0..S-1."""
         qkv = self.qkv_proj.forward_fused(x)  # [S, B, (nq + 2 nkv) D]
         cos_t, sin_t = self.rope_cache.tables(qkv.device)
         o = ops.rope_attention(qkv, cos_t, sin_t, self.num_heads_local, self.num_kv_heads_local, self.head_dim,
-                               causal=True)
+                               causal=True, key_ranges=key_ranges, positions=positions)
         return self.o_proj(o)
 
 
@@ -160,7 +162,7 @@ class LlamaDecoderLayer(nn.Module):
         self.post_attention_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps,
                                                 sequence_parallel_enabled=sp, dtype=dtype, device=device)
 
-    def forward(self, hidden_states, residual=None):
+    def forward(self, hidden_states, residual=None, key_ranges=None, positions=None):
         """Pre-norm block on the un-added stream: returns (mlp_out, residual) where the true hidden
         state is mlp_out + residual (the add is fused into the next norm kernel)."""
         if residual is None:
@@ -168,11 +170,14 @@ class LlamaDecoderLayer(nn.Module):
             residual = hidden_states
         else:
             normed, residual = self.input_layernorm(hidden_states, residual)
-        attn = self.self_attn(normed)
+        if key_ranges is None and positions is None:
+            attn = self.self_attn(normed)
+        else:
+            attn = self.self_attn(normed, key_ranges, positions)
         normed, residual = self.post_attention_layernorm(attn, residual)
         return self.mlp(normed), residual
 
-    def forward_stages(self, hidden_states, residual=None):
+    def forward_stages(self, hidden_states, residual=None, key_ranges=None, positions=None):
         """`forward` as a generator that yields after every op that issues a sequence-parallel
         collective (qkv all-gather, o_proj reduce-scatter, gate_up all-gather, down reduce-scatter),
         for the two-stream interleaving of parallel_layers/stream_split.py."""
@@ -186,7 +191,7 @@ class LlamaDecoderLayer(nn.Module):
         yield
         cos_t, sin_t = att.rope_cache.tables(qkv.device)
         o = ops.rope_attention(qkv, cos_t, sin_t, att.num_heads_local, att.num_kv_heads_local, att.head_dim,
-                               causal=True)
+                               causal=True, key_ranges=key_ranges, positions=positions)
         attn = att.o_proj(o)
         yield
         normed, residual = self.post_attention_layernorm(attn, residual)
@@ -219,8 +224,10 @@ class LlamaModel(nn.Module):
                             device=device)
         self.activation_checkpoint = getattr(config, "activation_checkpoint", None)  # None | "full"
 
-    def forward(self, input_ids: torch.Tensor) -> torch.Tensor:
-        """input_ids [B, S] -> final hidden [S(/tp), B, H] (sequence-parallel shard if SP)."""
+    def forward(self, input_ids: torch.Tensor, key_ranges=None, positions=None) -> torch.Tensor:
+        """input_ids [B, S] -> final hidden [S(/tp), B, H] (sequence-parallel shard if SP).
+        key_ranges / positions: see LlamaAttention.forward (the same objects go to every layer)."""
+        masked = key_ranges is not None or positions is not None
         ids = input_ids.t().contiguous()  # [S, B]
         hidden = self.embed_tokens(ids)
         residual = None
@@ -228,7 +235,12 @@ class LlamaModel(nn.Module):
             # index (not unpack) the (hidden, residual) pair: keeps the loop torch.fx-traceable for
             # pipeline partitioning, where each decoder layer is a leaf
             if self.activation_checkpoint == "full" and self.training:
-                res = checkpoint(layer, hidden, residual, use_reentrant=False)
+                if masked:
+                    res = checkpoint(layer, hidden, residual, key_ranges, positions, use_reentrant=False)
+                else:
+                    res = checkpoint(layer, hidden, residual, use_reentrant=False)
+            elif masked:
+                res = layer(hidden, residual, key_ranges, positions)
             else:
                 res = layer(hidden, residual)
             hidden, residual = res[0], res[1]
@@ -250,17 +262,41 @@ class LlamaForCausalLM(nn.Module):
             self.lm_head.weight._nxd_tied = True   # grad buffers defer this bucket's reduction
 
     def forward(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-                labels: Optional[torch.Tensor] = None, position_ids=None, **unused) -> CausalLMOutput:
+                labels: Optional[torch.Tensor] = None, position_ids=None, key_ranges=None, **unused) -> CausalLMOutput:
+        """key_ranges: explicit interval mask (ops.KeyRanges) for the attention of every layer;
+        otherwise, with config.document_masking_eos_token_id set, documents are cut after every EOS
+        token of input_ids.  position_ids: int [B, S] rotary positions; otherwise, with
+        config.reset_position_ids, positions restart at every document.  Labels and loss are
+        unchanged."""
+        key_ranges, positions = self._document_mask(input_ids, key_ranges, position_ids)
         k = self._interleave(input_ids, labels)
         if k:
-            return self._forward_interleaved(input_ids, attention_mask, labels, k)
-        hidden = self.model(input_ids)
+            return self._forward_interleaved(input_ids, attention_mask, labels, k, key_ranges, positions)
+        if key_ranges is None and positions is None:
+            hidden = self.model(input_ids)
+        else:
+            hidden = self.model(input_ids, key_ranges, positions)
         logits = self.lm_head(hidden)  # [S, B, V/tp]
         loss = None
         if labels is not None:
             tok_sum, n = self._loss_terms(logits, labels, attention_mask)
             loss = tok_sum / n
         return CausalLMOutput(loss=loss, logits=logits)
+
+    def _document_mask(self, input_ids, key_ranges, position_ids):
+        """(key_ranges, positions) of this forward, derived once on the device of input_ids."""
+        eos = getattr(self.config, "document_masking_eos_token_id", None)
+        if key_ranges is None and position_ids is None and eos is None:
+            return None, None
+        if get_pipeline_model_parallel_size() > 1:
+            raise NotImplementedError("document masking / position_ids are not supported with pipeline parallelism: "
+                                      "the mask is not carried between pipeline stages")
+        if key_ranges is None and eos is not None:
+            key_ranges = ops.ranges_from_eos(input_ids, int(eos))
+        positions = position_ids
+        if positions is None and key_ranges is not None and getattr(self.config, "reset_position_ids", False):
+            positions = ops.positions_from_ranges(key_ranges)
+        return key_ranges, positions
 
     @staticmethod
     def _loss_terms(logits, labels, attention_mask):
@@ -290,18 +326,19 @@ class LlamaForCausalLM(nn.Module):
             k -= 1
         return k if k >= 2 else 0
 
-    def _part(self, ids, labels, attention_mask):
+    def _part(self, ids, labels, attention_mask, key_ranges=None, positions=None):
         m = self.model
         hidden = m.embed_tokens(ids.t().contiguous())
         residual = None
         for layer in m.layers:
-            hidden, residual = yield from layer.forward_stages(hidden, residual)
+            hidden, residual = yield from layer.forward_stages(hidden, residual, key_ranges, positions)
         hidden = m.norm(hidden, residual)[0]
         logits = self.lm_head(hidden)
         yield
         return self._loss_terms(logits, labels, attention_mask)
 
-    def _forward_interleaved(self, input_ids, attention_mask, labels, k: int = 2) -> CausalLMOutput:
+    def _forward_interleaved(self, input_ids, attention_mask, labels, k: int = 2, key_ranges=None,
+                             positions=None) -> CausalLMOutput:
         """Training forward of TP + SP as k parts of the micro-batch on k streams, their collectives
         interleaved (parallel_layers/stream_split.py); same loss as the one-pass forward.
 
@@ -314,7 +351,11 @@ class LlamaForCausalLM(nn.Module):
         n = input_ids.shape[0] // k
         sl = [slice(i * n, (i + 1) * n) for i in range(k)]
         self.model.rope_cache.tables(input_ids.device)   # built once on this stream, read by every part
-        gens = [self._part(input_ids[s], labels[s], attention_mask[s] if attention_mask is not None else None)
+        if key_ranges is not None:
+            key_ranges.transposed()   # built once on this stream; the parts slice it along the batch
+        gens = [self._part(input_ids[s], labels[s], attention_mask[s] if attention_mask is not None else None,
+                           key_ranges[s] if key_ranges is not None else None,
+                           positions[s] if positions is not None else None)
                 for s in sl]
         terms = stream_split.run_interleaved(gens, input_ids.device)
         if input_ids.is_cuda:
@@ -367,7 +408,7 @@ def llama_config(name: str = "llama3-8b", **overrides):
     kw.update(overrides)
     cfg = LlamaConfig(**kw)
     for k in ("sequence_parallel_enabled", "selective_checkpoint_enabled", "kv_shared_group_size",
-              "activation_checkpoint"):
+              "activation_checkpoint", "document_masking_eos_token_id", "reset_position_ids"):
         if k in overrides:
             setattr(cfg, k, overrides[k])
     return cfg

@@ -8,6 +8,9 @@ from .decode import argmax_rows, decode_attention, greedy_advance_, kv_cache_wri
 from .embedding import vocab_parallel_embedding  # noqa: F401
 from .grouped_gemm import (grouped_linear, grouped_linear_reference, moe_dispatch, moe_permutation,  # noqa: F401
                            moe_unpermute_combine)
+from .attention_ranges import (KeyRanges, positions_from_ranges, ranges_from_cu_seqlens,  # noqa: F401
+                               ranges_from_document_starts, ranges_from_eos, ranges_from_lengths,
+                               ranges_sliding_window, validate)
 from .flash_attn import attention_reference, flash_attn_func, flash_attn_fwd_lse, rope_attention  # noqa: F401
 from .norm import rms_norm, rms_norm_reference  # noqa: F401
 from .optim import (adamw_flat_, clip_coefficient, flat_absmax, flat_sumsq, scale_flat_, sr_seed_for_step,  # noqa: F401
