@@ -67,7 +67,7 @@ void decode_attn_set_trace(uint64_t*);
 int dgemv_launch(int, const void*, int64_t, const void*, float, const void*, int64_t, void*, int64_t, int, int, int, int,
                  int, int, const float*, const float*, const int64_t*, int, void*, void*, int64_t, int64_t, int64_t,
                  const int*, int, int, const float*, float*, hipStream_t, const int64_t*, int64_t, void*, float*);
-int grouped_gemm_launch(int, const void*, const void*, void*, const int*, int, int, int, int, int, hipStream_t);
+int grouped_gemm_launch(int, const void*, const void*, void*, const int*, int, int, int, int, hipStream_t);
 int wgrad_gemm_launch(const void*, int64_t, const void*, int64_t, float*, int64_t, int, int, int, int, hipStream_t);
 int wgrad_gemm_choose_splits(int, int, int);
 int decode_attn_oproj_launch(const void*, const int64_t*, const void*, const void*, const int64_t*, const int*, const int*,
@@ -75,16 +75,12 @@ int decode_attn_oproj_launch(const void*, const int64_t*, const void*, const voi
 int grouped_rowgemm_launch(int, const void*, const void*, void*, const int*, int, int, int, int, hipStream_t);
 int wgrad_gemm_grouped_launch(const void*, int64_t, const void*, int64_t, float*, int64_t, int64_t, const int*, int, int,
                               int, int, hipStream_t);
-void wgrad_gemm_set_ablate(int);
 int dense_gemm_launch(int, int, const void*, int64_t, const void*, int64_t, void*, int64_t, int, int, int, int, hipStream_t);
 int dense_gemm_choose_splits(int, int, int);
-void dense_gemm_set_pipe(int);
 void decode_attn_set_oproj_maxl(int);
 int decode_attn_oproj_maxl();
 int decode_attn_sync_error(bool);
 void decode_attn_set_sync(int);
-void grouped_rowgemm_set_pp(int);
-void wgrad_gemm_set_pp(int);
 int cu_stream_launch(const void*, void*, int64_t, int, int64_t, hipStream_t);
 int moe_combine_fwd_launch(const void*, const int64_t*, const float*, void*, int64_t, int, int, hipStream_t);
 int moe_combine_bwd_launch(const void*, const void*, const int64_t*, const float*, void*, float*, int64_t, int, int,
@@ -819,7 +815,9 @@ void dense_gemm(int64_t layout, int64_t epi, at::Tensor a, at::Tensor b, at::Ten
            "dense_gemm");
 }
 
-// MoE grouped GEMMs over expert-sorted rows (csrc/grouped_gemm.hip); offs int32 [E + 1] on device.
+// MoE grouped GEMMs over expert-sorted rows; offs int32 [E + 1] on device.  Modes 0 / 1 run on
+// csrc/grouped_rowgemm.hip (csrc/grouped_gemm.hip when the reduction is no multiple of 32), mode 2
+// on the grouped mode of csrc/wgrad_gemm.hip.
 //   mode 0: a = x [M, K], b = W [E, K, N], c = y [M, N] bf16
 //   mode 1: a = dy [M, N], b = W [E, K, N], c = dx [M, K] bf16
 //   mode 2: a = x [M, K], b = dy [M, N], c = dW [E, K, N] fp32 (accumulate: +=)
@@ -857,11 +855,7 @@ void grouped_gemm(int64_t mode, at::Tensor a, at::Tensor b, at::Tensor offs, at:
   TORCH_CHECK(offs.size(0) == E + 1, "grouped_gemm: offs must have E + 1 entries");
   TORCH_CHECK(K % 8 == 0 && N % 8 == 0, "grouped_gemm: K and N must be multiples of 8");
   TORCH_CHECK(M < (1LL << 31) && K < (1LL << 31) && N < (1LL << 31) && E < 65536, "grouped_gemm: sizes too large");
-  static const bool wg_kernel = [] {
-    const char* e = getenv("NXD_GG_WGRAD");
-    return !(e && e[0] == '0');
-  }();
-  if (mode == 2 && wg_kernel) {
+  if (mode == 2) {
     // expert weight gradients on the token-major wgrad kernel (csrc/wgrad_gemm.hip, grouped mode):
     // dW[e] [K, N] += x_e^T dy_e
     if (!accumulate) c.zero_();
@@ -875,7 +869,7 @@ void grouped_gemm(int64_t mode, at::Tensor a, at::Tensor b, at::Tensor offs, at:
     const char* e = getenv("NXD_GG_ROW");
     return !(e && e[0] == '0');
   }();
-  if ((mode == 0 || mode == 1) && row_kernel) {
+  if (row_kernel) {
     // 256 x 256 tiles (csrc/grouped_rowgemm.hip); -1 = shape it does not take (reduction % 32)
     const int rc = nxd::grouped_rowgemm_launch((int)mode, a.data_ptr(), b.data_ptr(), c.data_ptr(),
                                                offs.data_ptr<int32_t>(), (int)E, (int)M, (int)K, (int)N, cur_stream());
@@ -885,7 +879,7 @@ void grouped_gemm(int64_t mode, at::Tensor a, at::Tensor b, at::Tensor offs, at:
     }
   }
   check_rc(nxd::grouped_gemm_launch((int)mode, a.data_ptr(), b.data_ptr(), c.data_ptr(), offs.data_ptr<int32_t>(), (int)E,
-                                    (int)M, (int)K, (int)N, accumulate ? 1 : 0, cur_stream()),
+                                    (int)M, (int)K, (int)N, cur_stream()),
            "grouped_gemm");
 }
 
@@ -1100,7 +1094,6 @@ PYBIND11_MODULE(_C, m) {
   m.def("wgrad_gemm", &wgrad_gemm);
   m.def("dense_gemm", &dense_gemm, py::arg("layout"), py::arg("epi"), py::arg("a"), py::arg("b"), py::arg("c"),
         py::arg("splits") = 0);
-  m.def("dense_gemm_set_pipe", [](int64_t v) { nxd::dense_gemm_set_pipe((int)v); });
   m.def("dense_gemm_splits", [](int64_t M, int64_t N, int64_t K) {
     return nxd::dense_gemm_choose_splits((int)M, (int)N, (int)K);
   });
@@ -1133,10 +1126,7 @@ PYBIND11_MODULE(_C, m) {
     check_rc(nxd::cu_stream_launch(src.data_ptr(), dst.data_ptr(), bytes_per_block, (int)blocks, ticks, cur_stream()),
              "cu_stream");
   });
-  m.def("wgrad_gemm_set_ablate", [](int64_t v) { nxd::wgrad_gemm_set_ablate((int)v); });
   // ping-pong (staggered wave-group) main loops of the two hand-written GEMMs, for in-process A/B
-  m.def("grouped_rowgemm_set_pp", [](int64_t v) { nxd::grouped_rowgemm_set_pp((int)v); });
-  m.def("wgrad_gemm_set_pp", [](int64_t v) { nxd::wgrad_gemm_set_pp((int)v); });
   m.def("wgrad_gemm_splits", [](int64_t T, int64_t M, int64_t N) { return nxd::wgrad_gemm_choose_splits((int)T, (int)M, (int)N); });
   m.def("moe_combine_fwd", &moe_combine_fwd);
   m.def("moe_combine_bwd", &moe_combine_bwd);

@@ -21,28 +21,37 @@
 //     B_lo (columns 0..127), B_hi (128..255) -- so every region is a contiguous slab of the source
 //     (128-B rows for NT, 256-B token rows for TN: whole cache lines, never half-lines), two
 //     K-tiles = 128 KiB;
-//   * per K-tile four phases, wave-uniform and identical for all waves:
-//       q0: read A_lo + B_lo fragments, MFMA A_lo x B_lo      q1: read B_hi, MFMA A_lo x B_hi
-//       q2: read A_hi, MFMA A_hi x B_hi                       q3: (no reads)  MFMA A_hi x B_lo
-//     so A_lo / B_lo are dead after q0, B_hi after q1, A_hi after q2, and each region is REFILLED
-//     with the K-tile two ahead as soon as it is dead: every phase issues one region (2 LDS-DMA
-//     pieces per thread), four regions = eight pieces stay in flight across the barriers, each
-//     waited for with a counted vmcnt (never 0 in the loop) ~4.5 phases after its issue;
-//   * ping-pong: waves 4..7 run one barrier behind waves 0..3, so on every SIMD one wave's 16-MFMA
-//     burst covers its partner's fragment reads and DMA issue; MFMA bursts at s_setprio 1;
+//   * per K-tile four phases, wave-uniform and identical for all eight waves (no wave-group
+//     stagger), ONE barrier per phase; the 16-MFMA burst of a phase carries the fragment reads of
+//     the next phase, interleaved, into registers that have just died (register-pipelined):
+//       q0: MFMA A_lo x B_lo, reads B_hi(t)          q1: MFMA A_lo x B_hi, reads A_hi(t) over A_lo
+//       q2: MFMA A_hi x B_hi, no reads               q3: MFMA A_hi x B_lo, reads A_lo / B_lo(t+1)
+//     so the MFMA pipe never waits on an LDS read after a barrier;
+//   * LDS-DMA: regions are issued in the order A_lo, B_lo, B_hi, A_hi (issue position 4 t + R,
+//     2 pieces per thread each); the prologue issues positions 0..6 and phase P = 4 t + q issues
+//     position P + 7 (A_hi(t+1) in q0, A_lo / B_lo / B_hi(t+2) in q1 / q2 / q3).  Before the
+//     barrier that ends phase P every thread waits, with a counted vmcnt (never 0 before the
+//     tail), for the regions read in phase P + 1; four younger regions = eight pieces per thread
+//     stay in flight across every barrier;
 //   * LDS images (written lane-linearly by global_load_lds_dwordx4, the swizzle applied to each
 //     lane's SOURCE address, rule 21):
 //       NT region [128 rows][64 k], 128-B rows, 16-B chunk c of row r stored at c ^ ((r >> 1) & 7):
 //          every 16-lane group of a ds_read_b128 fragment read covers all 64 banks once;
-//       TN region [64 k][128 features], 256-B rows, chunk c of row t at c ^ swz(t) (the wgrad
-//          kernel's swizzle): the two 32-lane groups of ds_read_b64_tr_b16 are conflict-free;
+//       TN region [64 k][128 features], 256-B rows, chunk c of row t at c ^ tok_swz(t) (the
+//          token-major image of csrc/gemm_tile.h): the transposed reads are conflict-free;
 //   * XCD-aware block remap + a raster band of row tiles; split-K outermost in the grid.
-// Ring safety (global barrier instance #n; waves 0..3 pass #(2P), #(2P+1) in phase P = 4t + q,
-// waves 4..7 one later): a region read in phase P is dead after #(2P+2); the refills are issued in
-// phase P + 2 or later (A_lo / B_lo of tile t + 2 in q2 / q3 of t, B_hi / A_hi of t + 1 in q0 / q1
-// of t).  Data read in phase P is waited for (vmcnt) by every thread before #(2P-1): waves 0..3 at
-// the end of their MFMA burst of P-1, waves 4..7 at the end of their load segment of P-1.
-#include "common.h"
+// Ring safety (barrier #P ends phase P = 4 t + q; all waves pass the same barriers): a region whose
+// fragments are read in phase P feeds the MFMAs of phase P + 1, which wait for those reads to
+// return, so its LDS is dead after #(P + 1).  Its refill is the region of the K-tile two ahead in
+// the same buffer, issued in phase P + 2 or later (i.e. after #(P + 1)): B_hi(t) is read in
+// q0 of t and B_hi(t+2) issued in q3 of t; A_hi(t) read in q1, A_hi(t+2) issued in q0 of t + 1;
+// A_lo / B_lo(t+1) read in q3 of t, A_lo / B_lo(t+3) issued in q1 / q2 of t + 1.  Data read in
+// phase P + 1 is waited for by every thread before #P, so the barrier publishes it.
+// Measured and dropped (profiles/r6_dense_gemm_pipes_vs_hipblaslt.jsonl,
+// profiles/r6_dense_gemm_pmc.txt): a ping-pong form of this loop (waves 4..7 one barrier behind
+// waves 0..3, two barriers per phase, reads before the burst), 2-9 % slower; four waves of 128 x 128
+// on v_mfma_f32_32x32x16_bf16 with one barrier per K-tile, 5-20 % slower.
+#include "gemm_tile.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -72,48 +81,19 @@ struct Params {
   int band;          // row tiles per raster band
 };
 
-typedef __attribute__((address_space(3))) char lds_char_t;
-typedef __attribute__((address_space(3))) short4_t lds_short4_t;
-__device__ __forceinline__ uint32_t lds_addr(const char* q) { return (uint32_t)(uintptr_t)(const lds_char_t*)q; }
-
-// one 1 KiB LDS-DMA piece (16 B per lane) at the wave-uniform LDS address `lds_dst`
-__device__ __forceinline__ void dma16(const void* src, uint32_t lds_dst) {
-  uint32_t sv;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(sv) : "v"(src), "s"(lds_dst) : "memory");
-}
-
 __device__ __forceinline__ int nt_swz(int r) { return (r >> 1) & 7; }
-__device__ __forceinline__ int tn_swz(int t) { return 2 * ((t & 3) | (((t >> 3) & 1) << 2)); }
 
 // NT fragment of region rows [r0, r0 + 16), k-half s: lane l -> row r0 + (l & 15), k 32 s + 8 (l >> 4) .. + 7
 __device__ __forceinline__ bf16x8_t frag_nt(const char* reg, int r0, int s) {
   const int l = threadIdx.x & 63, r = r0 + (l & 15), ch = (l >> 4) + 4 * s;
   return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4_t*>(reg + r * 128 + ((ch ^ nt_swz(r)) << 4)));
 }
-// TN fragment of region features [f0, f0 + 16), k-half s (two transposed reads): lane l -> feature
-// f0 + (l & 15) at k 32 s + 8 (l >> 4) + j
-__device__ __forceinline__ bf16x8_t frag_tn(const char* reg, int f0, int s) {
-  const int l = threadIdx.x & 63, g = l >> 4, i = l & 15, q = i >> 2, p = i & 3;
-  const int col = f0 + 4 * p, t = 32 * s + 8 * g + q;
-  const char* b0 = reg + t * 256 + (((col >> 3) ^ tn_swz(t)) << 4) + 8 * (p & 1);
-  const char* b1 = reg + (t + 4) * 256 + (((col >> 3) ^ tn_swz(t + 4)) << 4) + 8 * (p & 1);
-  const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)b0);
-  const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)b1);
-  const short __attribute__((ext_vector_type(8))) a8 = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, a8);
-}
-
+// fragment of region rows (NT) / features (TN) [x0, x0 + 16), k-half s; TN: two transposed reads of
+// the token-major image, lane l -> feature x0 + (l & 15) at k 32 s + 8 (l >> 4) + j
 template <int L>
 __device__ __forceinline__ bf16x8_t frag(const char* reg, int x0, int s) {
   if constexpr (L == LNT) return frag_nt(reg, x0, s);
-  else return frag_tn(reg, x0, s);
-}
-
-__device__ __forceinline__ void barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
+  else return frag_tr16<256>(reg, x0, 32 * s);
 }
 
 // wait until at most `younger` regions (2 pieces each) issued after the needed one are in flight
@@ -128,20 +108,14 @@ __device__ __forceinline__ void wait_regions(int younger) {
   }
 }
 
-template <int L, int E, int PIPE>
+template <int L, int E>
 __global__ void __launch_bounds__(NT, 1) gemm_kernel(Params p) {
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
   const int tiles = p.mt * p.nt;
   const int id = xcd_remap(blockIdx.x, gridDim.x);
   const int split = id / tiles;
   int rt, ct;
-  {
-    const int within = id - split * tiles;
-    const int kb = p.band, bnd = within / (kb * p.nt), rem = within - bnd * kb * p.nt;
-    const int h = min(kb, p.mt - bnd * kb);
-    rt = bnd * kb + rem % h;
-    ct = rem / h;
-  }
+  band_raster(id - split * tiles, p.mt, p.nt, p.band, rt, ct);
   const int m0 = rt * BM, n0 = ct * BN;
   const int k_begin = split * p.k_per_split;
   const int k_end = min(p.K, k_begin + p.k_per_split);
@@ -171,7 +145,7 @@ __global__ void __launch_bounds__(NT, 1) gemm_kernel(Params p) {
         sa[h][j] = p.a + (int64_t)min(m0 + 128 * h + pr, p.M - 1) * p.lda + k_begin + 8 * c;
         sb[h][j] = p.b + (int64_t)min(n0 + 128 * h + pr, p.N - 1) * p.ldb + k_begin + 8 * c;
       } else {
-        const int pr = 4 * piece + (lane >> 4), c = (lane & 15) ^ tn_swz(pr);
+        const int pr = 4 * piece + (lane >> 4), c = (lane & 15) ^ tok_swz(pr);
         sa[h][j] = p.a + (int64_t)(k_begin + pr) * p.lda + min(m0 + 128 * h + 8 * c, p.M - 8);
         sb[h][j] = p.b + (int64_t)(k_begin + pr) * p.ldb + min(n0 + 128 * h + 8 * c, p.N - 8);
       }
@@ -209,148 +183,77 @@ __global__ void __launch_bounds__(NT, 1) gemm_kernel(Params p) {
   using I2 = std::integral_constant<int, 2>;
   using I3 = std::integral_constant<int, 3>;
   bf16x8_t af[4][2], blo[2][2], bhi[2][2];
-  auto mfma_q = [&](auto qc, bf16x8_t (&bf)[2][2]) {
-    constexpr int qd = decltype(qc)::value;
-    __builtin_amdgcn_s_setprio(1);
+
+  // Main loop (structure and ring safety: file header).  Prologue: issue positions 0..6, A_lo(0) /
+  // B_lo(0) read into registers, B_hi(0) published.  Each A fragment is re-read right after its
+  // last use.
+  issue(I0{}, 0); issue(I1{}, 0); issue(I2{}, 0); issue(I3{}, 0); issue(I0{}, 1); issue(I1{}, 1); issue(I2{}, 1);
+  wait_for(1, 5);
+  barrier();
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) af[i][s] = frag<L>(smem + R_ALO, wr * 64 + 16 * i, s);
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) blo[j][s] = frag<L>(smem + R_BLO, wc * 32 + 16 * j, s);
+  wait_for(2);
+  barrier();
+  for (int t = 0; t < nk; ++t) {
+    const char* buf = smem + (t & 1) * BUF;
+    const char* nbuf = smem + ((t + 1) & 1) * BUF;
+    // ---- q0: A_lo x B_lo, reads B_hi(t)
+    issue(I3{}, t + 1);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[0][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][s], blo[j][s], acc[0][i][j], 0, 0, 0);
+        if (i < 2) bhi[i][s] = frag<L>(buf + R_BHI, wc * 32 + 16 * i, s);
+      }
+    wait_for(4 * t + 3);
+    barrier();
+    // ---- q1: A_lo x B_hi, reads A_hi(t) into af as each fragment dies
+    issue(I0{}, t + 2);
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[1][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][s], bhi[j][s], acc[1][i][j], 0, 0, 0);
+        af[i][s] = frag<L>(buf + R_AHI, wr * 64 + 16 * i, s);
+      }
+    barrier();
+    // ---- q2: A_hi x B_hi
+    issue(I1{}, t + 2);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          acc[qd][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][s], bf[j][s], acc[qd][i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-  };
-
-  if constexpr (PIPE == 0) {
-  // prologue: K-tile 0 whole, A_lo / B_lo of K-tile 1 (what the loop expects issued before t = 0)
-  issue(I0{}, 0); issue(I1{}, 0); issue(I2{}, 0); issue(I3{}, 0); issue(I0{}, 1); issue(I1{}, 1);
-  wait_for(1);
-  barrier();
-  const bool grp1 = wr == 1;
-  if (grp1) barrier();   // the stagger
-  for (int t = 0; t < nk; ++t) {
-    const char* buf = smem + (t & 1) * BUF;
-    // ---- q0: A_lo x B_lo
-    issue(I2{}, t + 1);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) af[i][s] = frag<L>(buf + R_ALO, wr * 64 + 16 * i, s);
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) blo[j][s] = frag<L>(buf + R_BLO, wc * 32 + 16 * j, s);
-    if (grp1) wait_for(4 * t + 2);
+          acc[2][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][s], bhi[j][s], acc[2][i][j], 0, 0, 0);
+    wait_for(4 * t + 5);
     barrier();
-    mfma_q(I0{}, blo);
-    if (!grp1) wait_for(4 * t + 2);
-    barrier();
-    // ---- q1: A_lo x B_hi
-    issue(I3{}, t + 1);
+    // ---- q3: A_hi x B_lo, reads A_lo(t+1) / B_lo(t+1) as fragments die
+    issue(I2{}, t + 2);
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int s = 0; s < 2; ++s)
 #pragma unroll
-      for (int s = 0; s < 2; ++s) bhi[j][s] = frag<L>(buf + R_BHI, wc * 32 + 16 * j, s);
-    if (grp1) wait_for(4 * t + 3);
-    barrier();
-    mfma_q(I1{}, bhi);
-    if (!grp1) wait_for(4 * t + 3);
-    barrier();
-    // ---- q2: A_hi x B_hi
-    issue(I0{}, t + 2);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) af[i][s] = frag<L>(buf + R_AHI, wr * 64 + 16 * i, s);
-    barrier();
-    mfma_q(I2{}, bhi);
-    barrier();
-    // ---- q3: A_hi x B_lo
-    issue(I1{}, t + 2);
-    if (grp1) wait_for(4 * t + 5);
-    barrier();
-    mfma_q(I3{}, blo);
-    if (!grp1) wait_for(4 * t + 5);
-    barrier();
-  }
-  if (!grp1) barrier();   // equal barrier counts before the epilogue
-  } else {
-    // PIPE 1: no wave-group stagger; every phase's MFMA burst carries the fragment reads of the next
-    // phase (register-pipelined), one barrier per phase.  Reads: B_hi(t) in q0, A_hi(t) in q1 (each
-    // A fragment re-read right after its last use), A_lo(t+1) / B_lo(t+1) in q3; a region read in
-    // phase P is consumed by P+1's MFMAs, so it is dead after the barrier ending P+1 and refilled in
-    // P+2 or later: phase P issues issue-position P + 7 (A_hi(t+1) in q0, A_lo / B_lo / B_hi(t+2) in
-    // q1 / q2 / q3).  Before the barrier ending phase P every thread waits for the regions read in
-    // P+1 (4 regions younger stay in flight).
-    issue(I0{}, 0); issue(I1{}, 0); issue(I2{}, 0); issue(I3{}, 0); issue(I0{}, 1); issue(I1{}, 1); issue(I2{}, 1);
-    wait_for(1, 5);
-    barrier();
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) af[i][s] = frag<L>(smem + R_ALO, wr * 64 + 16 * i, s);
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) blo[j][s] = frag<L>(smem + R_BLO, wc * 32 + 16 * j, s);
-    wait_for(2);
-    barrier();
-    for (int t = 0; t < nk; ++t) {
-      const char* buf = smem + (t & 1) * BUF;
-      const char* nbuf = smem + ((t + 1) & 1) * BUF;
-      // ---- q0: A_lo x B_lo, reads B_hi(t)
-      issue(I3{}, t + 1);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
+      for (int j = 0; j < 2; ++j) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[0][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][s], blo[j][s], acc[0][i][j], 0, 0, 0);
-          if (i < 2) bhi[i][s] = frag<L>(buf + R_BHI, wc * 32 + 16 * i, s);
+          acc[3][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][s], blo[j][s], acc[3][i][j], 0, 0, 0);
+          if (j == 1) af[i][s] = frag<L>(nbuf + R_ALO, wr * 64 + 16 * i, s);
         }
-      wait_for(4 * t + 3);
-      barrier();
-      // ---- q1: A_lo x B_hi, reads A_hi(t) into af as each fragment dies
-      issue(I0{}, t + 2);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[1][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][s], bhi[j][s], acc[1][i][j], 0, 0, 0);
-          af[i][s] = frag<L>(buf + R_AHI, wr * 64 + 16 * i, s);
-        }
-      barrier();
-      // ---- q2: A_hi x B_hi
-      issue(I1{}, t + 2);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[2][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][s], bhi[j][s], acc[2][i][j], 0, 0, 0);
-      wait_for(4 * t + 5);
-      barrier();
-      // ---- q3: A_hi x B_lo, reads A_lo(t+1) / B_lo(t+1) as fragments die
-      issue(I2{}, t + 2);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            acc[3][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][s], blo[j][s], acc[3][i][j], 0, 0, 0);
-            if (j == 1) af[i][s] = frag<L>(nbuf + R_ALO, wr * 64 + 16 * i, s);
-          }
-          blo[j][s] = frag<L>(nbuf + R_BLO, wc * 32 + 16 * j, s);
-        }
-      wait_for(4 * t + 6);
-      barrier();
-    }
+        blo[j][s] = frag<L>(nbuf + R_BLO, wc * 32 + 16 * j, s);
+      }
+    wait_for(4 * t + 6);
+    barrier();
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -407,211 +310,12 @@ __global__ void __launch_bounds__(NT, 1) gemm_kernel(Params p) {
   }
 }
 
-// ---- PIPE 2: four waves of 128 x 128 (one per SIMD) on v_mfma_f32_32x32x16_bf16 ------------------
-// The 8-wave kernel above spends ~30 % of its wave-cycles parked at barriers and fragment waits
-// (MFMA busy 57 % at 8192 x 4096 x 4096, SQ_WAIT_ANY 0.315 of wave cycles: profiles/r6_dense_gemm_pmc.txt).
-// Here each wave owns a 128 x 128 quarter of the tile -- 4 x 4 32x32 accumulator tiles, 256 registers
-// (a lone wave per SIMD has 512) -- and reads 8 fragments per 16 MFMAs of 32 cycles, each k-step's
-// fragments read into the other register set while the current one feeds the MFMAs:
-//   tile t, k-steps 0..3 (16 k each):  reads (t, ks+1) -> other set | 16 MFMAs on this set
-//   after k-step 2: lgkmcnt(0) + vmcnt(0) (this thread's pieces of tile t+1) + ONE barrier; k-step 3
-//   reads (t+1, 0) and issues the LDS-DMA of tile t+2 into tile t's buffer (all its reads retired)
-// so a tile's DMA has four k-steps (~2,000 cycles) to land.  (The 16x16x32 form of this structure
-// made hipcc shuttle the 64 four-register accumulators between AGPRs and VGPRs every iteration.)
-// LDS images as above except the TN swizzle: 256-B rows with chunk c of row t at
-// c ^ (((t & 3) << 2) | ((t >> 2) & 3)) (cdna_hip_programming.md T10 (b)), under which the 32-lane
-// halves of the 32x32x16 transposed operand reads are conflict-free.
-constexpr int NT4 = 256;
-
-__device__ __forceinline__ int tn4_swz(int t) { return ((t & 3) << 2) | ((t >> 2) & 3); }
-
-// 32x32x16 operand of region rows / features [x0, x0 + 32), k-step ks (16 k): lane l -> row / feature
-// x0 + (l & 31), k = 16 ks + 8 (l >> 5) + j
-template <int L>
-__device__ __forceinline__ bf16x8_t frag32(const char* reg, int x0, int ks) {
-  const int l = threadIdx.x & 63;
-  if constexpr (L == LNT) {
-    const int r = x0 + (l & 31), ch = 2 * ks + (l >> 5);
-    return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const u32x4_t*>(reg + r * 128 + ((ch ^ nt_swz(r)) << 4)));
-  } else {
-    const int g = l >> 4, q = (l >> 2) & 3, pp = l & 3;
-    const int t = 16 * ks + 8 * (g >> 1) + q;
-    const int ch = (x0 >> 3) + 2 * (g & 1) + (pp >> 1);
-    const char* b0 = reg + t * 256 + ((ch ^ tn4_swz(t)) << 4) + 8 * (pp & 1);
-    const char* b1 = reg + (t + 4) * 256 + ((ch ^ tn4_swz(t + 4)) << 4) + 8 * (pp & 1);
-    const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)b0);
-    const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)b1);
-    const short __attribute__((ext_vector_type(8))) a8 = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8_t, a8);
-  }
-}
-
-template <int L, int E>
-__global__ void __launch_bounds__(NT4, 1) gemm4_kernel(Params p) {
-  __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
-  const int tiles = p.mt * p.nt;
-  const int id = xcd_remap(blockIdx.x, gridDim.x);
-  const int split = id / tiles;
-  int rt, ct;
-  {
-    const int within = id - split * tiles;
-    const int kb = p.band, bnd = within / (kb * p.nt), rem = within - bnd * kb * p.nt;
-    const int h = min(kb, p.mt - bnd * kb);
-    rt = bnd * kb + rem % h;
-    ct = rem / h;
-  }
-  const int m0 = rt * BM, n0 = ct * BN;
-  const int k_begin = split * p.k_per_split;
-  const int k_end = min(p.K, k_begin + p.k_per_split);
-  const int nk = (k_end - k_begin) / BK;
-  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int wr = wid >> 1, wc = wid & 1;
-
-  f32x16_t acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // Per-lane DMA sources of K-tile 0.  Full tiles only (M, N % 256 == 0: the launcher checks), so the
-  // 4 pieces x 2 halves of one operand differ by uniform row / token offsets, except for the source
-  // swizzle: NT's depends on the piece's parity (2 pointers per operand), TN's on the piece (4).
-  constexpr int NV = L == LNT ? 2 : 4;
-  const uint16_t* sa[NV];
-  const uint16_t* sb[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    if constexpr (L == LNT) {
-      const int pr = 8 * (4 * wid + v) + (lane >> 3), c = (lane & 7) ^ nt_swz(pr);
-      sa[v] = p.a + (int64_t)(m0 + pr) * p.lda + k_begin + 8 * c;
-      sb[v] = p.b + (int64_t)(n0 + pr) * p.ldb + k_begin + 8 * c;
-    } else {
-      const int pr = 4 * (4 * wid + v) + (lane >> 4), c = (lane & 15) ^ tn4_swz(pr);
-      sa[v] = p.a + (int64_t)(k_begin + pr) * p.lda + m0 + 8 * c;
-      sb[v] = p.b + (int64_t)(k_begin + pr) * p.ldb + n0 + 8 * c;
-    }
-  }
-  auto pv = [](int j) { return L == LNT ? (j & 1) : j; };
-  auto poff = [&](int h, int j, int64_t ld) -> int64_t {
-    if constexpr (L == LNT) return (int64_t)(128 * h + 8 * (j & ~1)) * ld;
-    else return (int64_t)128 * h;
-  };
-  const int64_t adv_a = L == LNT ? (int64_t)BK : (int64_t)BK * p.lda;
-  const int64_t adv_b = L == LNT ? (int64_t)BK : (int64_t)BK * p.ldb;
-  const uint32_t lds0 = lds_addr(smem);
-  // piece q (0..15) of K-tile s: region q / 4 (A_lo, A_hi, B_lo, B_hi), piece j = q % 4
-  auto issue_piece = [&](int s, int q) {
-    const int r = q >> 2, j = q & 3, h = r & 1;
-    const uint32_t dst = lds0 + (s & 1) * BUF + (r == 0 ? R_ALO : r == 1 ? R_AHI : r == 2 ? R_BLO : R_BHI) + wid * 4096 + j * 1024;
-    const uint16_t* src = r < 2 ? sa[pv(j)] + (int64_t)s * adv_a + poff(h, j, p.lda)
-                                : sb[pv(j)] + (int64_t)s * adv_b + poff(h, j, p.ldb);
-    dma16(src, __builtin_amdgcn_readfirstlane(dst));
-  };
-  const int ra = wr ? R_AHI : R_ALO, rb = wc ? R_BHI : R_BLO;
-  bf16x8_t fa0[4], fb0[4], fa1[4], fb1[4];
-  auto rd = [&](const char* buf, int ks, bf16x8_t (&fa)[4], bf16x8_t (&fb)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) fa[i] = frag32<L>(buf + ra, 32 * i, ks);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) fb[j] = frag32<L>(buf + rb, 32 * j, ks);
-  };
-  auto mm = [&](bf16x8_t (&fa)[4], bf16x8_t (&fb)[4]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-  };
-
-#pragma unroll
-  for (int q = 0; q < 16; ++q) issue_piece(0, q);
-  if (nk > 1) {
-#pragma unroll
-    for (int q = 0; q < 16; ++q) issue_piece(1, q);
-    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  barrier();
-  rd(smem, 0, fa0, fb0);
-  for (int t = 0; t < nk; ++t) {
-    const char* buf = smem + (t & 1) * BUF;
-    rd(buf, 1, fa1, fb1);
-    mm(fa0, fb0);
-    rd(buf, 2, fa0, fb0);
-    mm(fa1, fb1);
-    rd(buf, 3, fa1, fb1);
-    mm(fa0, fb0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this thread's pieces of tile t+1
-    barrier();
-    rd(smem + ((t + 1) & 1) * BUF, 0, fa0, fb0);      // past the last tile: stale LDS, never consumed
-    if (t + 2 < nk) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) issue_piece(t + 2, q);
-    }
-    mm(fa1, fb1);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  // ---- epilogue: per wave 4 passes of 32 rows x 128 columns through a padded fp32 LDS slab
-  constexpr int LD = 132;
-  float* slab = reinterpret_cast<float*>(smem) + wid * (32 * LD);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        slab[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * LD + 32 * j + (lane & 31)] = acc[i][j][r];
-    __builtin_amdgcn_wave_barrier();
-    const int row0 = m0 + 128 * wr + 32 * i, col0 = n0 + 128 * wc;
-    if constexpr (E == F32_ATOMIC) {
-      float* cp = static_cast<float*>(p.c);
-#pragma unroll 2
-      for (int rr = 0; rr < 64; ++rr) {   // half a row (256 contiguous bytes) per wave-instruction
-        const int lr = rr >> 1, col = col0 + 64 * (rr & 1) + lane, row = row0 + lr;
-        const float v = slab[lr * LD + 64 * (rr & 1) + lane];
-        if (row < p.M && col < p.N) unsafeAtomicAdd(cp + (int64_t)row * p.ldc + col, v);
-      }
-    } else {
-#pragma unroll
-      for (int ps = 0; ps < 8; ++ps) {   // 16 lanes x 8 columns per row, 4 rows per pass
-        const int lr = 4 * ps + (lane >> 4), c8 = 8 * (lane & 15);
-        const int row = row0 + lr, col = col0 + c8;
-        const f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(slab + lr * LD + c8);
-        const f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(slab + lr * LD + c8 + 4);
-        if (row < p.M && col < p.N) {
-          if constexpr (E == BF16) {
-            u32x4_t o;
-            o[0] = pack2bf(v0[0], v0[1]); o[1] = pack2bf(v0[2], v0[3]);
-            o[2] = pack2bf(v1[0], v1[1]); o[3] = pack2bf(v1[2], v1[3]);
-            *reinterpret_cast<u32x4_t*>(static_cast<uint16_t*>(p.c) + (int64_t)row * p.ldc + col) = o;
-          } else {
-            f32x4_t* cp = reinterpret_cast<f32x4_t*>(static_cast<float*>(p.c) + (int64_t)row * p.ldc + col);
-            const f32x4_t c0 = cp[0], c1 = cp[1];
-            cp[0] = c0 + v0;
-            cp[1] = c1 + v1;
-          }
-        }
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
-static int g_pipe = -1;   // main-loop variant override (dense_gemm_set_pipe, in-process A/B)
-
 static int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
 }
 
 }  // namespace dg
-
-void dense_gemm_set_pipe(int v) { dg::g_pipe = v; }
 
 // K splits of the atomic epilogue: grid waves of 256 workgroups x (K-steps per split + the atomic
 // epilogue's cost in K-steps, ~6); splits stay 1 unless they save at least a tenth.
@@ -659,17 +363,8 @@ int dense_gemm_launch(int layout, int epi, const void* a, int64_t lda, const voi
   p.band = band;
   const int64_t nwg = (int64_t)p.mt * p.nt * p.splits;
   if (nwg > INT32_MAX) return -2;
-  // default: the 8-wave register-pipelined loop (PIPE 1), the fastest of the three on every measured
-  // shape (profiles/r6_dense_gemm_pipes_vs_hipblaslt.jsonl: PIPE 2 5-20 % slower, PIPE 0 2-9 %)
-  static int pipe_env = dg::env_int("NXD_DG_PIPE", 1);
-  int pipe = dg::g_pipe >= 0 ? dg::g_pipe : pipe_env;
-  if (pipe == 2 && (M % dg::BM || N % dg::BN)) pipe = 1;   // the 4-wave kernel takes whole tiles only
-#define NXD_DG_LAUNCH(LY, EP)                                                                                  \
-  do {                                                                                                       \
-    if (pipe == 2) hipLaunchKernelGGL((dg::gemm4_kernel<LY, EP>), dim3((unsigned)nwg), dim3(dg::NT4), 0, stream, p); \
-    else if (pipe) hipLaunchKernelGGL((dg::gemm_kernel<LY, EP, 1>), dim3((unsigned)nwg), dim3(dg::NT), 0, stream, p); \
-    else hipLaunchKernelGGL((dg::gemm_kernel<LY, EP, 0>), dim3((unsigned)nwg), dim3(dg::NT), 0, stream, p);      \
-  } while (0)
+#define NXD_DG_LAUNCH(LY, EP) \
+  hipLaunchKernelGGL((dg::gemm_kernel<LY, EP>), dim3((unsigned)nwg), dim3(dg::NT), 0, stream, p)
   if (layout == dg::LNT) {
     if (epi == dg::BF16) NXD_DG_LAUNCH(dg::LNT, dg::BF16);
     else if (epi == dg::F32_ACC) NXD_DG_LAUNCH(dg::LNT, dg::F32_ACC);

@@ -30,7 +30,7 @@
 //     body with every atomic ablated runs 1.59 ms).  Going lower needs fewer atomic BYTES, not a
 //     faster body: 256 keys per workgroup is the register-file maximum for resident dK/dV
 //     (256 keys x 128 d x 2 x 4 B = half of a CU's 512 KiB of registers).
-#include "common.h"
+#include "gemm_tile.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -119,9 +119,7 @@ typedef short bf16s8_t __attribute__((ext_vector_type(8)));
 
 // LDS access through a plain 32-bit byte address (the extern LDS symbol's address is folded
 // into the per-lane base registers once, so `base + constant` becomes the ds_* immediate offset
-// instead of a v_add per access).
-typedef __attribute__((address_space(3))) char lds_char_t;
-__device__ __forceinline__ uint32_t lds_addr(const char* p) { return (uint32_t)(uintptr_t)(const lds_char_t*)p; }
+// instead of a v_add per access); lds_addr of csrc/gemm_tile.h gives that address.
 template <typename T>
 __device__ __forceinline__ T lds_ld(uint32_t a) {
   return *(const __attribute__((address_space(3))) T*)(uintptr_t)a;
@@ -357,12 +355,8 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
   // buffer.  Issued from inline asm: when the compiler sees an LDS-DMA in flight it waits for it
   // (vmcnt(0)) before every transposed LDS read, which exposed the whole prefetch once per tile.
   // Completion is tracked by hand (the counted vmcnt wait at the end of each tile).  M0 carries the
-  // wave-uniform LDS destination and is restored after the issue.
-  auto dma16 = [&](const void* src, uint32_t lds_dst) {
-    uint32_t sv;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(sv) : "v"(src), "s"(lds_dst) : "memory");
-  };
+  // wave-uniform LDS destination and is restored after the issue.  16-B pieces: dma16 of
+  // csrc/gemm_tile.h; the 4-B row constants:
   auto dma4 = [&](const void* src, uint32_t lds_dst) {
     uint32_t sv;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"

@@ -20,7 +20,7 @@
 //     (T1, shared L2), heavy causal q-blocks first.
 //   * arbitrary (batch, seq, head) strides, so Q/K/V can be read straight out of a fused
 //     [S, B, (Hq+2Hkv)*D] QKV projection output and O written into [S, B, Hq*D].
-#include "common.h"
+#include "gemm_tile.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -67,9 +67,6 @@ template <int D>
 __device__ __forceinline__ int lds_off(int row, int ch) {  // byte offset of a 16-B chunk
   return row * (D * 2) + swz<D>(row, ch) * 16;
 }
-
-typedef __attribute__((address_space(3))) char lds_char_t;
-__device__ __forceinline__ uint32_t lds_addr(const char* ptr) { return (uint32_t)(uintptr_t)(const lds_char_t*)ptr; }
 
 // ds_read_b64_tr_b16 as inline asm: the builtin form makes the compiler put an s_waitcnt vmcnt(0)
 // (it cannot tell the read from the in-flight LDS-DMA of the next tile) in front of the first V

@@ -16,7 +16,8 @@ def _rel(got, ref):
     return ((got.float() - ref).abs().max() / ref.abs().max()).item()
 
 
-@pytest.mark.parametrize("M,N,K", [(512, 512, 256), (300, 264, 192), (1024, 768, 4096), (257, 1032, 64)])
+@pytest.mark.parametrize("M,N,K", [(512, 512, 256), (300, 264, 192), (1024, 768, 4096), (257, 1032, 64),
+                                   (300, 264, 128)])   # K / 64 = 1..4 and 64 reduction steps
 def test_dense_gemm_nt_bf16(M, N, K):
     g = torch.Generator(device="cuda").manual_seed(M * 7 + N)
     a = torch.randn(M, K, device="cuda", generator=g).to(torch.bfloat16)
@@ -27,8 +28,13 @@ def test_dense_gemm_nt_bf16(M, N, K):
     assert _rel(c, ref) < 1e-2
 
 
-@pytest.mark.parametrize("epi,splits", [(1, 1), (2, 0), (2, 3)])
-@pytest.mark.parametrize("T,M,N", [(512, 256, 256), (384, 264, 520), (4096, 768, 1024)])
+@pytest.mark.parametrize("T,M,N,epi,splits", [
+    (T, M, N, epi, splits)
+    for (epi, splits) in [(1, 1), (2, 0), (2, 3)]
+    for (T, M, N) in [(512, 256, 256), (384, 264, 520), (4096, 768, 1024)]
+] + [   # T / 64 = 1 and 2 reduction steps: the prologue and tail branches of the main loop
+    (64, 264, 520, 1, 1), (128, 264, 520, 1, 1), (64, 264, 520, 2, 0), (128, 264, 520, 2, 0),
+])
 def test_dense_gemm_tn_fp32(T, M, N, epi, splits):
     g = torch.Generator(device="cuda").manual_seed(T + M + N + epi)
     dy = torch.randn(T, M, device="cuda", generator=g).to(torch.bfloat16)

@@ -43,6 +43,8 @@ def _ref_fwd(x, w, offs):
     ([0, 0, 0, 0], 128, 128),                          # no rows at all
     ([4096], 512, 640),                                # one big group
     ([1000, 0, 37, 700, 3, 513], 512, 1056),           # 256-tile kernels: ragged rows, partial column tiles
+    ([70, 0, 300, 1], 32, 96),                         # 1 (fwd) / 3 (dgrad) reduction steps, output under one tile, a one-row group
+    ([70, 0, 300, 1], 64, 32),                         # 2 (fwd) / 1 (dgrad) reduction steps
 ])
 def test_grouped_gemm_fwd_dgrad_wgrad(counts, K, N):
     E = len(counts)

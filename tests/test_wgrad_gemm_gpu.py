@@ -17,6 +17,10 @@ def _ext():
     (1024, 768, 512, 4),     # token splits (fp32 atomics from 4 workgroups per element)
     (512, 264, 136, 0),      # partial tiles on both output dims, auto splits
     (2048, 256, 1024, 0),    # skinny output, auto split count
+    (32, 264, 136, 1),       # 1..4 token steps: the ring loop's prologue and tail branches,
+    (64, 264, 136, 1),       # partial tiles on both output dims
+    (96, 264, 136, 1),
+    (128, 264, 136, 1),
 ])
 def test_wgrad_gemm_matches_fp64(T, M, N, splits):
     torch.manual_seed(T + M + N)
