@@ -77,6 +77,9 @@ def parse(argv=None):
                    help="llama: attention does not cross the documents of a packed row (a document ends with this token id)")
     p.add_argument("--reset-position-ids", action="store_true",
                    help="llama, with --document-masking-eos-id: rotary positions restart at every document")
+    p.add_argument("--sliding-window", type=int, default=None,
+                   help="llama / mixtral: a token attends to itself and the N - 1 tokens before it (Mistral, Mixtral); "
+                        "0 removes the window of a loaded config")
     return p.parse_args(argv)
 
 
@@ -120,6 +123,10 @@ def model_config(a):
             raise SystemExit("--document-masking-eos-id is implemented for --model_family llama only")
         cfg.document_masking_eos_token_id = a.document_masking_eos_id
         cfg.reset_position_ids = a.reset_position_ids
+    if getattr(a, "sliding_window", None) is not None:
+        if a.model_family == "gpt_neox":
+            raise SystemExit("--sliding-window is implemented for --model_family llama and mixtral")
+        cfg.sliding_window = a.sliding_window or None
     if a.model_family == "mixtral":
         cfg.capacity_factor = a.capacity_factor
         cfg.moe_router = a.moe_router

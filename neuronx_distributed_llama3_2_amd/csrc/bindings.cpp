@@ -47,7 +47,8 @@ int scale_flat_launch(float*, int64_t, const float*, hipStream_t);
 int embedding_fwd_launch(const int64_t*, const void*, void*, int64_t, int, int64_t, int64_t, hipStream_t);
 int embedding_bwd_launch(const int64_t*, const void*, float*, int64_t, int, int64_t, int64_t, hipStream_t);
 int decode_attn_launch(const void*, const int64_t*, const void*, const void*, const int64_t*, const int*, const int*,
-                       float*, float*, float*, int*, void*, const int64_t*, int, int, int, int, int, int, float, hipStream_t);
+                       float*, float*, float*, int*, void*, const int64_t*, int, int, int, int, int, int, float, hipStream_t,
+                       int);
 int kv_cache_write_launch(const void*, const void*, const int64_t*, void*, void*, const int64_t*, const int*, const int*,
                           int, int, int, int, int, hipStream_t);
 int argmax_launch(const void*, int, int64_t, int, int, int64_t*, hipStream_t);
@@ -71,7 +72,8 @@ int grouped_gemm_launch(int, const void*, const void*, void*, const int*, int, i
 int wgrad_gemm_launch(const void*, int64_t, const void*, int64_t, float*, int64_t, int, int, int, int, hipStream_t);
 int wgrad_gemm_choose_splits(int, int, int);
 int decode_attn_oproj_launch(const void*, const int64_t*, const void*, const void*, const int64_t*, const int*, const int*,
-                             const void*, int64_t, int, float*, float*, float*, float*, float*, int, int, int, int, int, int, float, hipStream_t);
+                             const void*, int64_t, int, float*, float*, float*, float*, float*, int, int, int, int, int, int, float, hipStream_t,
+                             int);
 int grouped_rowgemm_launch(int, const void*, const void*, void*, const int*, int, int, int, int, hipStream_t);
 int wgrad_gemm_grouped_launch(const void*, int64_t, const void*, int64_t, float*, int64_t, int64_t, const int*, int, int,
                               int, int, hipStream_t);
@@ -511,7 +513,7 @@ void decode_attn_prefetch(c10::optional<at::Tensor> a, int64_t a_bytes, c10::opt
 // Fused decode attention + o_proj (csrc/decode_attn.hip FUSE): oacc [B*T, Hout] fp32 (zero on entry)
 // += o_proj(attention).  Returns false (nothing launched) for shapes the fused kernel does not cover.
 bool decode_attn_oproj(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional<at::Tensor> cache_idx, at::Tensor seq_len,
-                       at::Tensor wo, at::Tensor oacc, double scale) {
+                       at::Tensor wo, at::Tensor oacc, double scale, int64_t window) {
   int64_t qs[3];
   bshd_strides(q, "q", qs);
   check_bf16(kc, "k_cache");
@@ -522,6 +524,7 @@ bool decode_attn_oproj(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional
   const int B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
   const int Hkv = kc.size(1), Lmax = kc.size(2);
   TORCH_CHECK(kc.size(3) == D, "head dim mismatch");
+  TORCH_CHECK(window >= 0, "window must be >= 0 (0: none)");
   TORCH_CHECK(wo.dim() == 2 && wo.stride(1) == 1 && wo.size(1) == (int64_t)Hq * D, "wo must be [Hout, Hq * D]");
   check_aligned16(wo, "wo");
   const int64_t Hout = wo.size(0);
@@ -550,14 +553,15 @@ bool decode_attn_oproj(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional
   }
   const int rc = nxd::decode_attn_oproj_launch(q.data_ptr(), qs, kc.data_ptr(), vc.data_ptr(), cs, ci, seq_len.data_ptr<int>(),
                                                wo.data_ptr(), wo.stride(0), (int)Hout, oacc.data_ptr<float>(), po, pm, pl, mo, B, T,
-                                               Hq, Hkv, D, Lmax, (float)scale, cur_stream());
+                                               Hq, Hkv, D, Lmax, (float)scale, cur_stream(),
+                                               window >= Lmax ? 0 : (int)window);
   if (rc == -1) return false;
   check_rc(rc, "decode_attn_oproj");
   return true;
 }
 
 void decode_attn(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional<at::Tensor> cache_idx, at::Tensor seq_len,
-                 at::Tensor out, double scale, int64_t nsplit) {
+                 at::Tensor out, double scale, int64_t nsplit, int64_t window) {
   int64_t qs[3], os[3];
   bshd_strides(q, "q", qs);
   bshd_strides(out, "out", os);
@@ -571,6 +575,7 @@ void decode_attn(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional<at::T
   TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "q heads must be a multiple of kv heads");
   TORCH_CHECK((int64_t)(Hq / Hkv) * T <= 64, "decode supports (Hq/Hkv) * new_tokens <= 64");
   TORCH_CHECK(nsplit >= 1 && nsplit * 128 >= Lmax, "nsplit * 128 must cover the cache length");
+  TORCH_CHECK(window >= 0, "window must be >= 0 (0: none)");
   TORCH_CHECK(seq_len.scalar_type() == at::kInt && seq_len.numel() == B && seq_len.is_contiguous(), "seq_len must be int32 [B]");
   const int* ci = nullptr;
   if (cache_idx.has_value()) {
@@ -591,7 +596,8 @@ void decode_attn(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional<at::T
   int* counters = decode_counters(q.device().index(), (int64_t)B * Hkv);
   check_rc(nxd::decode_attn_launch(q.data_ptr(), qs, kc.data_ptr(), vc.data_ptr(), cs, ci, seq_len.data_ptr<int>(),
                                    po.data_ptr<float>(), pm.data_ptr<float>(), pl.data_ptr<float>(), counters, out.data_ptr(),
-                                   os, B, T, Hq, Hkv, D, (int)nsplit, (float)scale, cur_stream()),
+                                   os, B, T, Hq, Hkv, D, (int)nsplit, (float)scale, cur_stream(),
+                                   window >= Lmax ? 0 : (int)window),
            "decode_attn");
   nxd::decode_attn_set_prefetch(nullptr, 0, nullptr, 0, 0);   // armed ranges never outlive one call
 }
@@ -1169,8 +1175,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("scale_flat", &scale_flat);
   m.def("embedding_fwd", &embedding_fwd);
   m.def("embedding_bwd", &embedding_bwd);
-  m.def("decode_attn", &decode_attn);
-  m.def("decode_attn_oproj", &decode_attn_oproj);
+  // window: sliding-window attention, a query sees itself and the window - 1 keys before it (0 = none)
+  m.def("decode_attn", &decode_attn, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cache_idx"),
+        py::arg("seq_len"), py::arg("out"), py::arg("scale"), py::arg("nsplit"), py::arg("window") = 0);
+  m.def("decode_attn_oproj", &decode_attn_oproj, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cache_idx"),
+        py::arg("seq_len"), py::arg("wo"), py::arg("oacc"), py::arg("scale"), py::arg("window") = 0);
   m.def("decode_attn_sync_error", [](bool reset) { return nxd::decode_attn_sync_error(reset); }, py::arg("reset") = false);
   m.def("decode_attn_set_sync", [](int64_t v) { nxd::decode_attn_set_sync((int)v); });
   m.def("decode_attn_set_oproj_maxl", [](int64_t v) { nxd::decode_attn_set_oproj_maxl((int)v); });

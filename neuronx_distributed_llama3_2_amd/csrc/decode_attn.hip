@@ -74,6 +74,12 @@ struct Params {
   unsigned* sync_cnt;
   int* sync_err;
   float* mo;          // SYNC: [B * Hkv, M, D] merged attention rows (the merger's hand-off)
+  // sliding window (0 = none, the WIN = false kernels; never with SYNC): query row at absolute position lim - 1 sees the keys
+  // max(0, lim - window) <= key < lim, and the workgroup's sweep starts at the first 64-key chunk any row
+  // of this sequence can see (read from the device seq_len: static shapes, graph-capturable) -- the
+  // launchers size kps / nsplit by the window, not the cache (window_span).  Value-initialised to 0
+  // by every launcher, as the rule above asks.
+  int window;
 };
 static_assert(std::is_trivially_copyable<Params>::value && sizeof(Params) <= 4096, "kernel-argument struct");
 
@@ -156,9 +162,12 @@ __device__ __forceinline__ void oproj_tail(const Params& p, const float* of, con
 // 17.9 with every workgroup merging all partials itself -- vs 5.7 + 5.6 us; 0.759 vs 0.686
 // ms/token; profiles/r6_decode/sync_ab.txt): the in-launch wait on the slowest split of a head costs
 // more than a kernel boundary, so it is off by default (NXD_DECODE_ATTN_SYNC=1).
-template <int D, int NWV, bool FUSE, bool WO_LATE = true, bool SYNC = false>
+// WIN: sliding window (Params::window > 0).  A template flag, not a run-time test, so that the
+// un-windowed instantiations keep the code they had.
+template <int D, int NWV, bool FUSE, bool WO_LATE = true, bool SYNC = false, bool WIN = false>
 __global__ void __launch_bounds__(64 * NWV) attn_kernel(Params p) {
   static_assert(!SYNC || FUSE, "SYNC is a FUSE form");
+  static_assert(!WIN || !SYNC, "no SYNC form with a sliding window");
   constexpr int NS = D / 32;      // k-steps of the score MFMA
   constexpr int NDT = D / 16;     // 16-wide d tiles of the output
   constexpr int VL = D / 8;       // 16-B V loads per lane for 64 keys x D
@@ -206,6 +215,9 @@ __global__ void __launch_bounds__(64 * NWV) attn_kernel(Params p) {
     qf[s] = __builtin_bit_cast(bf16x8_t, v);
   }
   const int lim = slen - (p.T - 1 - tt_q);        // keys visible to query row mi (causal over new tokens)
+  const int lo_row = WIN ? max(0, lim - p.window) : 0;   // ... and not more than window back
+  // first key of the sweep: the chunk holding the earliest key row 0 (the oldest new token) sees
+  const int kbeg = WIN ? max(0, slen - (p.T - 1) - p.window) / KB * KB : 0;
 
   float run_m = -INFINITY, run_l = 0.f;           // stats of query row mi (log2 domain)
   f32x4_t o[NDT];
@@ -213,7 +225,7 @@ __global__ void __launch_bounds__(64 * NWV) attn_kernel(Params p) {
   for (int i = 0; i < NDT; ++i) o[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   // FUSE: the whole cache in one pass per workgroup (no key splits, no merge launch)
-  const int kend = (FUSE && !SYNC) ? slen : min(slen, (split + 1) * p.kps);
+  const int kend = (FUSE && !SYNC) ? slen : min(slen, kbeg + (split + 1) * p.kps);
   // K fragments and the V chunk of the NEXT chunk are loaded while this one runs its softmax and P.V
   u32x4_t kf[4][NS], vv[VL];
   auto load_chunk = [&](int k0) {
@@ -229,7 +241,7 @@ __global__ void __launch_bounds__(64 * NWV) attn_kernel(Params p) {
       for (int s = 0; s < NS; ++s) kf[kt][s] = *reinterpret_cast<const u32x4_t*>(kr + 32 * s);
     }
   };
-  int k0 = split * p.kps + wid * KB;
+  int k0 = kbeg + split * p.kps + wid * KB;
   if (k0 < kend) load_chunk(k0);
   // FUSE: the Wo block is issued AFTER the q and first K / V loads.  vmcnt retires in issue order:
   // issued first (round 3), the cold-HBM Wo loads had to land before the first score MFMA could
@@ -261,7 +273,7 @@ __global__ void __launch_bounds__(64 * NWV) attn_kernel(Params p) {
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
         const int key = k0 + kt * 16 + 4 * g + v;
-        const float sv = key < lim ? sc[kt][v] * p.scale_log2 : -INFINITY;
+        const float sv = (key < lim && (!WIN || key >= lo_row)) ? sc[kt][v] * p.scale_log2 : -INFINITY;
         sc[kt][v] = sv;
         cm = fmaxf(cm, sv);
       }
@@ -485,6 +497,18 @@ static int keys_per_split(int Lmax, int B, int Hkv) {
   return kps < 128 ? 128 : (kps > KPS ? KPS : kps);
 }
 
+// Keys a windowed launch has to cover: from the 64-aligned first visible key of the oldest new token
+// to seq_len is < roundup(window + T - 1, 64) + 64, whatever the cache holds.  A window that covers the
+// whole cache is no window (returns Lmax and clears it: the un-windowed kernel arguments).
+static int window_span(int Lmax, int T, int& window) {
+  if (window <= 0 || window >= Lmax) {
+    window = 0;
+    return Lmax;
+  }
+  const int64_t span = ((int64_t)window + T - 1 + KB - 1) / KB * KB + KB;
+  return span < Lmax ? (int)span : Lmax;
+}
+
 // Split attention's partials -> merged attention row block (bf16-rounded, as the merge kernel's
 // output the o_proj GEMV would read) -> this workgroup's o_proj partial, fp32 atomics into oacc: the
 // long-context form of FUSE (one launch instead of the merge + o_proj pair).  Grid (batch, kv head,
@@ -616,13 +640,15 @@ void decode_attn_set_prefetch(const void* a, int64_t a_bytes, const void* b, int
 }
 
 // Returns -1 when the shape is not covered (caller falls back to the 128-key-chunk kernel).
+// window > 0: sliding-window attention (Params::window); kps / nsplit follow the window's key span.
 int decode_attn2_launch(const void* q, const int64_t* qs, const void* kc, const void* vc, const int64_t* cs,
                         const int* cache_idx, const int* seq_len, float* po, float* pm, float* pl, void* out,
                         const int64_t* os, int B, int T, int Hq, int Hkv, int D, int Lmax, float scale, int* nsplit_out,
-                        hipStream_t stream) {
+                        hipStream_t stream, int window) {
   if (Hkv <= 0 || Hq % Hkv) return -1;
   const int M = (Hq / Hkv) * T;
   if (M > 16 || (D != 64 && D != 128)) return -1;
+  const int Leff = dattn::window_span(Lmax, T, window);
   dattn::Params p{};   // value-initialised: every field a launcher does not set is zero / null
   p.q = (const uint16_t*)q; p.q_sb = qs[0]; p.q_st = qs[1]; p.q_sh = qs[2];
   p.kc = (const uint16_t*)kc; p.vc = (const uint16_t*)vc;
@@ -631,9 +657,10 @@ int decode_attn2_launch(const void* q, const int64_t* qs, const void* kc, const 
   p.out = (uint16_t*)out; p.o_sb = os[0]; p.o_st = os[1]; p.o_sh = os[2];
   p.po = po; p.pm = pm; p.pl = pl;
   p.B = B; p.T = T; p.Hq = Hq; p.Hkv = Hkv;
-  const int kps = dattn::keys_per_split(Lmax, B, Hkv);
+  const int kps = dattn::keys_per_split(Leff, B, Hkv);
   p.kps = kps;
-  p.nsplit = (Lmax + kps - 1) / kps;
+  p.nsplit = (Leff + kps - 1) / kps;
+  p.window = window;
   p.scale_log2 = scale * 1.4426950408889634f;
   *nsplit_out = p.nsplit;
   // D = 64: 8 waves (<= 2 chunks each per 1024-key split); D = 128: 4 waves (LDS: V tiles + merge)
@@ -652,7 +679,15 @@ int decode_attn2_launch(const void* q, const int64_t* qs, const void* kc, const 
   dattn::g_pf[0] = dattn::g_pf[1] = nullptr;
   dattn::g_pf_bytes[0] = dattn::g_pf_bytes[1] = 0;
   const dim3 grid(p.attn_wgs + pf_wgs), block(64 * nwv);
-  if (D == 64) {
+  if (window) {
+    if (D == 64) {
+      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((dattn::attn_kernel<64, 8, false, true, false, true>), grid, block, lds, stream, p);
+    } else {
+      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<128, 4, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((dattn::attn_kernel<128, 4, false, true, false, true>), grid, block, lds, stream, p);
+    }
+  } else if (D == 64) {
     (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((dattn::attn_kernel<64, 8, false>), grid, block, lds, stream, p);
   } else {
@@ -694,14 +729,19 @@ int decode_attn_oproj_maxl() {
 // the whole cache; past that the split attention, whose keys per split fill the GPU, + merge + o_proj
 // launches win -- 0.726 vs 0.774 ms/token at the notebook's 2,304-key cache,
 // profiles/r6_decode/attn_split_ab.txt), M = G*T <= 16, D in {64, 128}, Wo blocks of <= 4 register
-// passes.
+// passes.  window > 0 (sliding window): Lmax above is the window's key span (window_span), and the
+// SYNC form is never taken.
 int decode_attn_oproj_launch(const void* q, const int64_t* qs, const void* kc, const void* vc, const int64_t* cs,
                              const int* cache_idx, const int* seq_len, const void* wo, int64_t ldwo, int Hout, float* oacc,
                              float* po, float* pm, float* pl, float* mo, int B, int T, int Hq, int Hkv, int D, int Lmax,
-                             float scale, hipStream_t stream) {
+                             float scale, hipStream_t stream, int window) {
   if (Hkv <= 0 || Hq % Hkv) return -1;
   const int G = Hq / Hkv, M = G * T;
   const int maxl = decode_attn_oproj_maxl();
+  // with a sliding window every size below is that of the window's key span, not of the cache: the
+  // one-pass form serves any cache whose window fits maxl
+  const int Lcache = Lmax;
+  Lmax = dattn::window_span(Lcache, T, window);
   // past maxl: split attention into the partials, then merge + o_proj (needs the partial buffers:
   // [B * Hkv * ceil(Lmax / 128) * M] rows of D, plus the two stats)
   const bool split = Lmax > maxl && po != nullptr && dattn::keys_per_split(Lmax, B, Hkv) < Lmax;
@@ -728,6 +768,7 @@ int decode_attn_oproj_launch(const void* q, const int64_t* qs, const void* kc, c
   p.c_sb = cs[0]; p.c_sh = cs[1]; p.c_sl = cs[2];
   p.cache_idx = cache_idx; p.seq_len = seq_len;
   p.B = B; p.T = T; p.Hq = Hq; p.Hkv = Hkv; p.nsplit = 1;
+  p.window = window;
   p.scale_log2 = scale * 1.4426950408889634f;
   p.wo = (const uint16_t*)wo; p.ldwo = ldwo; p.oacc = oacc; p.Hout = Hout; p.R = R; p.NP = Hout / R / rpp;
   p.attn_wgs = B * Hkv * R;
@@ -744,7 +785,7 @@ int decode_attn_oproj_launch(const void* q, const int64_t* qs, const void* kc, c
     (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n;
   }();
-  if (split && sync_on && mo != nullptr && B * Hkv <= dattn::kSyncHeads && (int)grid.x <= n_cu) {
+  if (split && sync_on && window == 0 && mo != nullptr && B * Hkv <= dattn::kSyncHeads && (int)grid.x <= n_cu) {
     // one launch: workgroup r of a head computes key split r (>= 128 keys, the partial buffers hold
     // Lmax / 128 splits), then merges the head's splits and runs its o_proj slice (SYNC above)
     int kps = (Lmax + R - 1) / R;
@@ -774,7 +815,7 @@ int decode_attn_oproj_launch(const void* q, const int64_t* qs, const void* kc, c
     int ns2 = 0;
     const int64_t no_out[3] = {0, 0, 0};
     const int rc = decode_attn2_launch(q, qs, kc, vc, cs, cache_idx, seq_len, po, pm, pl, nullptr, no_out, B, T, Hq, Hkv,
-                                       D, Lmax, scale, &ns2, stream);
+                                       D, Lcache, scale, &ns2, stream, window);
     if (rc != 0) return rc;
     if (ns2 != ns) return 3;   // the attention launch split differently: never write the output through null
     p.nsplit = ns; p.po = po; p.pm = pm; p.pl = pl;
@@ -792,7 +833,15 @@ int decode_attn_oproj_launch(const void* q, const int64_t* qs, const void* kc, c
     const char* e = getenv("NXD_DECODE_WO_LATE");
     return e ? atoi(e) != 0 : true;
   }();
-  if (D == 64) {
+  if (window) {   // the Wo block always after the first K / V loads
+    if (D == 64) {
+      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((dattn::attn_kernel<64, 8, true, true, false, true>), grid, block, lds, stream, p);
+    } else {
+      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<128, 4, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((dattn::attn_kernel<128, 4, true, true, false, true>), grid, block, lds, stream, p);
+    }
+  } else if (D == 64) {
     if (wo_late) {
       (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       hipLaunchKernelGGL((dattn::attn_kernel<64, 8, true, true>), grid, block, lds, stream, p);

@@ -34,6 +34,7 @@ struct DecodeParams {
   int B, T, Hq, Hkv, nsplit;
   float scale;
   int fused_merge;           // 1: last workgroup merges the splits; 0: separate merge_kernel
+  int window;                // sliding window: a row sees max(0, lim - window) <= key < lim (0 = none)
 };
 
 // Merge the (m, l, o) partials of all splits of one (batch, kv head): every phase parallel over the
@@ -156,7 +157,9 @@ __global__ void __launch_bounds__(256) attn_kernel(DecodeParams p, int* __restri
   const uint16_t* kbase = p.kc + (int64_t)cb * p.c_sb + (int64_t)hkv * p.c_sh;
   const uint16_t* vbase = p.vc + (int64_t)cb * p.c_sb + (int64_t)hkv * p.c_sh;
 
-  if (k0 < slen) {
+  // sliding window: chunks wholly below the earliest key of the oldest new token publish empty partials
+  const int lo0 = p.window ? max(0, slen - (p.T - 1) - p.window) : 0;
+  if (k0 < slen && k0 + kChunk > lo0) {
     // ---- V chunk for the P.V phase: issue the loads early (independent of the scores)
     const int c = tid % NC, kg = tid / NC;
     constexpr int VPT = kChunk / KG;   // keys per thread
@@ -197,7 +200,8 @@ __global__ void __launch_bounds__(256) attn_kernel(DecodeParams p, int* __restri
       s += __shfl_xor(s, 1, 64);
       const int tt = m / G;
       const int lim = slen - (p.T - 1 - tt);  // causal among the new tokens
-      if (half == 0) ss[m * kChunk + kk] = key < lim ? s : -INFINITY;
+      const int lo = p.window ? max(0, lim - p.window) : 0;
+      if (half == 0) ss[m * kChunk + kk] = (key < lim && key >= lo) ? s : -INFINITY;
     }
     __syncthreads();
     // ---- softmax per row (wave per row)
@@ -521,24 +525,27 @@ __global__ void __launch_bounds__(1024) topk_sample_kernel(const T* __restrict__
 }  // namespace dec
 
 int decode_attn2_launch(const void*, const int64_t*, const void*, const void*, const int64_t*, const int*, const int*,
-                        float*, float*, float*, void*, const int64_t*, int, int, int, int, int, int, float, int*, hipStream_t);
+                        float*, float*, float*, void*, const int64_t*, int, int, int, int, int, int, float, int*, hipStream_t,
+                        int);
 
 static int g_attn_v2 = [] { const char* e = getenv("NXD_DECODE_ATTN_V2"); return e ? atoi(e) : 1; }();
 void decode_attn_set_v2(int v) { g_attn_v2 = v; }
 
 int decode_attn_launch(const void* q, const int64_t* qs, const void* kc, const void* vc, const int64_t* cs,
                        const int* cache_idx, const int* seq_len, float* po, float* pm, float* pl, int* counters, void* out,
-                       const int64_t* os, int B, int T, int Hq, int Hkv, int D, int nsplit, float scale, hipStream_t stream) {
+                       const int64_t* os, int B, int T, int Hq, int Hkv, int D, int nsplit, float scale, hipStream_t stream,
+                       int window) {
   using namespace dec;
   if (Hkv <= 0 || Hq % Hkv) return -1;
   const int M = (Hq / Hkv) * T;
+  if (window < 0 || window >= nsplit * kChunk) window = 0;   // covers the cache: no window
   // small query groups: the MFMA flash-decoding kernel (decode_attn.hip), merge only past 1024 keys
   if (g_attn_v2) {
     int ns2 = 0;
     const int rc = decode_attn2_launch(q, qs, kc, vc, cs, cache_idx, seq_len, po, pm, pl, out, os, B, T, Hq, Hkv, D,
-                                       nsplit * kChunk, scale, &ns2, stream);
+                                       nsplit * kChunk, scale, &ns2, stream, window);
     if (rc == 0 && ns2 > 1) {
-      DecodeParams mp;
+      DecodeParams mp{};
       mp.q = (const uint16_t*)q; mp.q_sb = qs[0]; mp.q_st = qs[1]; mp.q_sh = qs[2];
       mp.kc = (const uint16_t*)kc; mp.vc = (const uint16_t*)vc;
       mp.c_sb = cs[0]; mp.c_sh = cs[1]; mp.c_sl = cs[2];
@@ -558,7 +565,7 @@ int decode_attn_launch(const void* q, const int64_t* qs, const void* kc, const v
   p.kc = (const uint16_t*)kc; p.vc = (const uint16_t*)vc;
   p.c_sb = cs[0]; p.c_sh = cs[1]; p.c_sl = cs[2];
   p.cache_idx = cache_idx; p.seq_len = seq_len; p.po = po; p.pm = pm; p.pl = pl;
-  p.B = B; p.T = T; p.Hq = Hq; p.Hkv = Hkv; p.nsplit = nsplit; p.scale = scale;
+  p.B = B; p.T = T; p.Hq = Hq; p.Hkv = Hkv; p.nsplit = nsplit; p.scale = scale; p.window = window;
   // separate merge launch by default: the fused last-workgroup merge needs agent-scope fences (L2
   // write-back / invalidate across the 8 XCDs), measured 2-3x slower on MI355X (tools/bench_decode.py)
   static const int mode = [] { const char* e = getenv("NXD_DECODE_FUSED_MERGE"); return e ? atoi(e) : 0; }();

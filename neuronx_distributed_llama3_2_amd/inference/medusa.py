@@ -93,6 +93,10 @@ class MedusaDecoder:
     def __init__(self, target, heads: MedusaHeads, choices: Optional[Sequence[Sequence[int]]] = None,
                  topk: int = TOPK):
         self.target, self.heads, self.topk = target, heads, topk
+        window = int(getattr(target.model, "sliding_window", 0) or 0)
+        if 0 < window < target.cache_len:
+            raise NotImplementedError(f"Medusa tree verification does not apply the model's sliding window ({window} "
+                                      f"keys, shorter than the {target.cache_len}-key cache)")
         bufs = medusa_tree_buffers(choices or DEFAULT_MEDUSA_CHOICES, topk)
         dev = target.device
         self.mask = bufs["attn_mask"].to(dev).bool()

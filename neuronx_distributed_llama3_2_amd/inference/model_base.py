@@ -17,6 +17,11 @@ RoPE + KV-cache write after QKV, residual adds after o_proj / down -- so a layer
 
 KV cache: ONE allocation [layers, 2, max_batch, kv_heads_local, max_len, head_dim] (bf16);
 `seq_ids` selects cache rows (continuous batching).
+
+Sliding window (`config.sliding_window`, Mistral / Mixtral): prefill masks with the interval-masked
+flash attention (`ops.ranges_sliding_window`), decode passes the window to the decode attention
+kernels, which then read only the last `window` keys of each sequence.  The cache keeps all max_len
+positions (no rolling buffer).
 """
 
 from __future__ import annotations
@@ -68,6 +73,9 @@ class DecoderInferenceMixin:
         self.tp = get_tensor_model_parallel_size()
         self.kv_cache: Optional[torch.Tensor] = None
         self.eps = float(config.rms_norm_eps)
+        # a query sees itself and the sliding_window - 1 keys before it; 0: every earlier key
+        self.sliding_window = int(getattr(config, "sliding_window", None) or 0)
+        self._prefill_ranges = {}
         self.eval()
         for p in self.parameters():
             p.requires_grad_(False)
@@ -85,6 +93,22 @@ class DecoderInferenceMixin:
     def reset_kv_cache(self) -> None:
         if self.kv_cache is not None:
             self.kv_cache.zero_()
+
+    # ------------------------------------------------------------------ sliding window
+    def _decode_window(self) -> int:
+        """The window of the decode attention launches: 0 when there is none or it covers the cache."""
+        return ops.decode_window(self.sliding_window, self.kv_cache.shape[4])
+
+    def _window_ranges(self, B: int, T: int, device):
+        """Key ranges of a T-token prefill under the sliding window (None when it hides nothing), one
+        object per (B, T, device): a captured prefill graph keeps reading the tensors it recorded."""
+        if not 0 < self.sliding_window < T:
+            return None
+        key = (B, T, str(device))
+        kr = self._prefill_ranges.get(key)
+        if kr is None:
+            kr = self._prefill_ranges[key] = ops.ranges_sliding_window(B, T, self.sliding_window, device=device)
+        return kr
 
     # ------------------------------------------------------------------ collectives
     def _all_reduce(self, x: torch.Tensor) -> torch.Tensor:
@@ -124,6 +148,8 @@ class DecoderInferenceMixin:
         x = ops.vocab_parallel_embedding(input_ids, emb.weight, emb.start_index)
         x = self._all_reduce(x)
         residual = None
+        win_ranges = self._window_ranges(B, T, input_ids.device) if prefill else None
+        window = self._decode_window()
         for i, layer in enumerate(self.model.layers):
             attn = layer.self_attn
             h, residual = self._norm(x, layer.input_layernorm.weight, residual)
@@ -135,9 +161,9 @@ class DecoderInferenceMixin:
             kc, vc = self.kv_cache[i, 0], self.kv_cache[i, 1]
             ops.kv_cache_write(k, v, kc, vc, pos0, sid32)
             if prefill:
-                o, _ = ops.flash_attn_fwd_lse(q, k, v, causal=True)
+                o, _ = ops.flash_attn_fwd_lse(q, k, v, causal=True, key_ranges=win_ranges)
             else:
-                o = ops.decode_attention(q, kc, vc, cache_len, sid32)
+                o = ops.decode_attention(q, kc, vc, cache_len, sid32, window=window)
             x = self._row(attn.o_proj, o.reshape(B, T, nq * D))
             h, residual = self._norm(x, layer.post_attention_layernorm.weight, residual)
             x = self._ffn(layer, h)
@@ -212,6 +238,8 @@ class DecoderInferenceMixin:
         else:
             res = ops.vocab_parallel_embedding(input_ids, ew, emb.start_index).reshape(M, -1).contiguous()
         qkv = torch.empty((M, W), dtype=res.dtype, device=res.device)
+        window = self._decode_window()
+        win = (window,) if window else ()   # no window: the kernels' un-windowed arguments
         for i, layer in enumerate(self.model.layers):
             attn = layer.self_attn
             w_qkv = attn.qkv_proj._fused_weight_bias()[0] if hasattr(attn.qkv_proj, "_fused_weight_bias") \
@@ -234,14 +262,14 @@ class DecoderInferenceMixin:
                       and not getattr(self, "_decode_deterministic", False))
             oacc = self._decode_oacc(M, res) if fuse_o else None
             if oacc is not None and C.decode_attn_oproj(q, kc, vc, sid32, cache_len.to(torch.int32), attn.o_proj.weight,
-                                                        oacc, 1.0 / math.sqrt(D)):
+                                                        oacc, 1.0 / math.sqrt(D), *win):
                 # oacc += o_proj(attention) (one launch); the GLU prologue sees res + oacc, the down
                 # epilogue folds it into res with the unfused rounding and zeroes it
                 a = torch.empty((M, w_d.shape[1]), dtype=res.dtype, device=res.device)
                 C.dgemv(2, res, ln2, self.eps, w_gu, a, 0, 0, 0, None, None, None, 1, None, None, None, oacc, None)
                 C.dgemv(1, a, None, 0.0, w_d, res, 0, 0, 0, None, None, None, 1, None, None, None, None, oacc)
                 continue
-            o = ops.decode_attention(q, kc, vc, cache_len, sid32)
+            o = ops.decode_attention(q, kc, vc, cache_len, sid32, window=window)
             C.dgemv(1, o.reshape(M, nq * D), None, 0.0, attn.o_proj.weight, res, 0, 0, 0, None, None, None, 1,
                     None, None, None)                                   # res += o_proj(o)
             a = torch.empty((M, w_d.shape[1]), dtype=res.dtype, device=res.device)
@@ -334,6 +362,8 @@ class DecoderInferenceMixin:
         qkv = torch.empty((M, W), dtype=res.dtype, device=res.device)
         clen32 = cache_len.to(torch.int32)
         fuse_o = _ATTN_OPROJ and B <= _ATTN_OPROJ_MAXB and not getattr(self, "_decode_deterministic", False)
+        window = self._decode_window()
+        win = (window,) if window else ()
         for i, layer in enumerate(self.model.layers):
             attn = layer.self_attn
             w_qkv = attn.qkv_proj._fused_weight_bias()[0] if hasattr(attn.qkv_proj, "_fused_weight_bias") \
@@ -343,8 +373,9 @@ class DecoderInferenceMixin:
                     kc, vc, sid32)
             q = qkv.view(B, T, nq + 2 * nkv, D)[:, :, :nq]
             ln2, w_gu, w_d = self._fused_ffn_weights(layer)
-            if not (fuse_o and C.decode_attn_oproj(q, kc, vc, sid32, clen32, attn.o_proj.weight, oacc, 1.0 / math.sqrt(D))):
-                o = ops.decode_attention(q, kc, vc, cache_len, sid32)
+            if not (fuse_o and C.decode_attn_oproj(q, kc, vc, sid32, clen32, attn.o_proj.weight, oacc, 1.0 / math.sqrt(D),
+                                                   *win)):
+                o = ops.decode_attention(q, kc, vc, cache_len, sid32, window=window)
                 C.dgemv(0, o.reshape(M, nq * D), None, 0.0, attn.o_proj.weight, oacc[:M], 0, 0, 0, None, None, None, 1,
                         None, None, None)                             # fp32 partial (overwrites)
             ar.sum_(oacc[:M], osum[:M], zero_in=True)                 # osum = o_proj; oacc re-zeroed
@@ -374,6 +405,8 @@ class DecoderInferenceMixin:
         Every node also sees the cached prefix [0, prefix_len).  Nothing is written to the KV cache;
         returns (logits [N, V], final hidden [N, H], per-layer (k, v) [N, Hkv, D] of the nodes) so
         the caller commits only the accepted path (commit_tree_kv)."""
+        if self._decode_window():
+            raise NotImplementedError("tree verification does not apply config.sliding_window")
         N = tokens.shape[0]
         nq, nkv, D = self.nq, self.nkv, self.head_dim
         g = nq // nkv

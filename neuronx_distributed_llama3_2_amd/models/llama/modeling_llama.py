@@ -247,6 +247,43 @@ class LlamaModel(nn.Module):
         return self.norm(hidden, residual)[0]
 
 
+def binding_window(config, num_keys) -> Optional[int]:
+    """config.sliding_window (Mistral / Mixtral: a query sees itself and the window - 1 keys before
+    it) when it hides keys of a num_keys-long sequence, else None."""
+    window = getattr(config, "sliding_window", None)
+    if not window:
+        return None
+    if isinstance(num_keys, torch.fx.Proxy):
+        # pipeline partitioning traces the forward without a sequence length: the longest sequence decides
+        num_keys = int(getattr(config, "max_position_embeddings", 0)) or int(window) + 1
+    return int(window) if int(window) < num_keys else None
+
+
+def attention_mask_inputs(config, input_ids, key_ranges, position_ids):
+    """(key_ranges, positions) of one causal-LM forward, derived once on the device of input_ids:
+    the explicit or EOS-derived document ranges, cut to config.sliding_window when it is shorter than
+    the sequence.  Rotary positions that restart per document (config.reset_position_ids) follow the
+    documents alone, not the window.  (None, None): plain causal attention at positions 0..S-1."""
+    eos = getattr(config, "document_masking_eos_token_id", None)
+    window = binding_window(config, input_ids.shape[1])
+    if key_ranges is None and position_ids is None and eos is None and window is None:
+        return None, None
+    if get_pipeline_model_parallel_size() > 1:
+        raise NotImplementedError("document masking / position_ids / a sliding window shorter than the sequence are "
+                                  "not supported with pipeline parallelism: the mask is not carried between "
+                                  "pipeline stages")
+    if key_ranges is None and eos is not None:
+        key_ranges = ops.ranges_from_eos(input_ids, int(eos))
+    positions = position_ids
+    if positions is None and key_ranges is not None and getattr(config, "reset_position_ids", False):
+        positions = ops.positions_from_ranges(key_ranges)
+    if window is not None:
+        B, S = input_ids.shape
+        win = ops.ranges_sliding_window(B, S, window, device=input_ids.device)
+        key_ranges = win if key_ranges is None else ops.intersect_ranges(key_ranges, win)
+    return key_ranges, positions
+
+
 class LlamaForCausalLM(nn.Module):
     def __init__(self, config, dtype=torch.bfloat16, device=None):
         super().__init__()
@@ -285,18 +322,7 @@ class LlamaForCausalLM(nn.Module):
 
     def _document_mask(self, input_ids, key_ranges, position_ids):
         """(key_ranges, positions) of this forward, derived once on the device of input_ids."""
-        eos = getattr(self.config, "document_masking_eos_token_id", None)
-        if key_ranges is None and position_ids is None and eos is None:
-            return None, None
-        if get_pipeline_model_parallel_size() > 1:
-            raise NotImplementedError("document masking / position_ids are not supported with pipeline parallelism: "
-                                      "the mask is not carried between pipeline stages")
-        if key_ranges is None and eos is not None:
-            key_ranges = ops.ranges_from_eos(input_ids, int(eos))
-        positions = position_ids
-        if positions is None and key_ranges is not None and getattr(self.config, "reset_position_ids", False):
-            positions = ops.positions_from_ranges(key_ranges)
-        return key_ranges, positions
+        return attention_mask_inputs(self.config, input_ids, key_ranges, position_ids)
 
     @staticmethod
     def _loss_terms(logits, labels, attention_mask):
@@ -397,6 +423,10 @@ def llama_config(name: str = "llama3-8b", **overrides):
         "tiny": dict(hidden_size=256, intermediate_size=512, num_hidden_layers=2, num_attention_heads=4,
                      num_key_value_heads=2, vocab_size=1024, rope_theta=10000.0, max_position_embeddings=512,
                      rms_norm_eps=1e-5),
+        # Mistral-7B-v0.1 is the Llama architecture plus a sliding attention window
+        "mistral-7b": dict(hidden_size=4096, intermediate_size=14336, num_hidden_layers=32, num_attention_heads=32,
+                           num_key_value_heads=8, vocab_size=32000, rope_theta=10000.0, max_position_embeddings=32768,
+                           sliding_window=4096, rms_norm_eps=1e-5),
         # Llama-3-8B's head geometry scaled down (32 / 8 heads of 128 -> 16 / 8 of 64): TP = 8 keeps one
         # KV head per rank as the headline config does (multi-rank rehearsals, tests)
         "tiny8": dict(hidden_size=1024, intermediate_size=2048, num_hidden_layers=2, num_attention_heads=16,
@@ -408,7 +438,7 @@ def llama_config(name: str = "llama3-8b", **overrides):
     kw.update(overrides)
     cfg = LlamaConfig(**kw)
     for k in ("sequence_parallel_enabled", "selective_checkpoint_enabled", "kv_shared_group_size",
-              "activation_checkpoint", "document_masking_eos_token_id", "reset_position_ids"):
-        if k in overrides:
-            setattr(cfg, k, overrides[k])
+              "activation_checkpoint", "document_masking_eos_token_id", "reset_position_ids", "sliding_window"):
+        if k in kw:
+            setattr(cfg, k, kw[k])
     return cfg

@@ -22,7 +22,7 @@ from ...parallel_layers.layer_norm import RMSNorm
 from ...parallel_layers.layers import ColumnParallelLinear, ParallelEmbedding
 from ...parallel_layers.loss_functions import parallel_cross_entropy
 from ...parallel_layers.parallel_state import get_tensor_model_parallel_size
-from ..llama.modeling_llama import CausalLMOutput, LlamaAttention, RopeCache, _init_normal
+from ..llama.modeling_llama import CausalLMOutput, LlamaAttention, RopeCache, _init_normal, attention_mask_inputs
 
 
 class MixtralDecoderLayer(nn.Module):
@@ -45,13 +45,16 @@ class MixtralDecoderLayer(nn.Module):
         self.post_attention_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps,
                                                 sequence_parallel_enabled=sp, dtype=dtype, device=device)
 
-    def forward(self, hidden_states, residual=None):
+    def forward(self, hidden_states, residual=None, key_ranges=None, positions=None):
         if residual is None:
             normed = self.input_layernorm(hidden_states)
             residual = hidden_states
         else:
             normed, residual = self.input_layernorm(hidden_states, residual)
-        attn = self.self_attn(normed)
+        if key_ranges is None and positions is None:
+            attn = self.self_attn(normed)
+        else:
+            attn = self.self_attn(normed, key_ranges, positions)
         normed, residual = self.post_attention_layernorm(attn, residual)
         out, router_logits = self.block_sparse_moe(normed)
         return out, residual, router_logits
@@ -73,13 +76,20 @@ class MixtralModel(nn.Module):
                             device=device)
         self.activation_checkpoint = getattr(config, "activation_checkpoint", None)
 
-    def forward(self, input_ids):
+    def forward(self, input_ids, key_ranges=None, positions=None):
+        """key_ranges / positions: see LlamaAttention.forward (the same objects go to every layer)."""
+        masked = key_ranges is not None or positions is not None
         hidden = self.embed_tokens(input_ids.t().contiguous())
         residual = None
         logits_all = []
         for layer in self.layers:
             if self.activation_checkpoint == "full" and self.training:
-                res = checkpoint(layer, hidden, residual, use_reentrant=False)
+                if masked:
+                    res = checkpoint(layer, hidden, residual, key_ranges, positions, use_reentrant=False)
+                else:
+                    res = checkpoint(layer, hidden, residual, use_reentrant=False)
+            elif masked:
+                res = layer(hidden, residual, key_ranges, positions)
             else:
                 res = layer(hidden, residual)
             hidden, residual = res[0], res[1]
@@ -97,8 +107,16 @@ class MixtralForCausalLM(nn.Module):
         self.lm_head = ColumnParallelLinear(config.hidden_size, config.vocab_size, bias=False, gather_output=False,
                                            init_method=init, sequence_parallel_enabled=sp, dtype=dtype, device=device)
 
-    def forward(self, input_ids, attention_mask=None, labels=None, **unused):
-        hidden, router_logits = self.model(input_ids)
+    def forward(self, input_ids, attention_mask=None, labels=None, key_ranges=None, **unused):
+        """key_ranges: explicit interval mask (ops.KeyRanges) for the attention of every layer.
+        config.sliding_window, when shorter than the sequence, cuts every query's keys to the last
+        `sliding_window` (intersected with key_ranges if both are given); a config without it runs
+        plain causal attention."""
+        key_ranges, positions = attention_mask_inputs(self.config, input_ids, key_ranges, None)
+        if key_ranges is None and positions is None:
+            hidden, router_logits = self.model(input_ids)
+        else:
+            hidden, router_logits = self.model(input_ids, key_ranges, positions)
         logits = self.lm_head(hidden)
         loss = None
         if labels is not None:
@@ -132,7 +150,8 @@ def mixtral_config(name: str = "mixtral-8x7b", **overrides):
     kw.setdefault("initializer_range", 0.02)
     kw.setdefault("router_aux_loss_coef", 0.02)
     extra = {k: overrides.pop(k) for k in list(overrides) if k in ("sequence_parallel_enabled", "capacity_factor",
-                                                                   "moe_router", "activation_checkpoint")}
+                                                                   "moe_router", "activation_checkpoint",
+                                                                   "sliding_window")}
     kw.update(overrides)
     cfg = MixtralConfig(**kw)
     for k, v in extra.items():

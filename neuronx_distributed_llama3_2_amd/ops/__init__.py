@@ -4,11 +4,12 @@ PyTorch fp32 reference on the CPU (see _ext.use_native)."""
 from ._ext import ext, ext_available, use_native  # noqa: F401
 from .activations import swiglu, swiglu_reference  # noqa: F401
 from .cross_entropy import parallel_cross_entropy_reference, vocab_parallel_cross_entropy  # noqa: F401
-from .decode import argmax_rows, decode_attention, greedy_advance_, kv_cache_write, topk_sample  # noqa: F401
+from .decode import (argmax_rows, decode_attention, decode_window, greedy_advance_, kv_cache_write,  # noqa: F401
+                     topk_sample)
 from .embedding import vocab_parallel_embedding  # noqa: F401
 from .grouped_gemm import (grouped_linear, grouped_linear_reference, moe_dispatch, moe_permutation,  # noqa: F401
                            moe_unpermute_combine)
-from .attention_ranges import (KeyRanges, positions_from_ranges, ranges_from_cu_seqlens,  # noqa: F401
+from .attention_ranges import (KeyRanges, intersect_ranges, positions_from_ranges, ranges_from_cu_seqlens,  # noqa: F401
                                ranges_from_document_starts, ranges_from_eos, ranges_from_lengths,
                                ranges_sliding_window, validate)
 from .flash_attn import attention_reference, flash_attn_func, flash_attn_fwd_lse, rope_attention  # noqa: F401

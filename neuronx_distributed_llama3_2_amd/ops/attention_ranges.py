@@ -161,6 +161,17 @@ def ranges_sliding_window(B: int, S: int, window: int, device=None) -> KeyRanges
     return KeyRanges(lo, hi, S)
 
 
+def intersect_ranges(a: KeyRanges, b: KeyRanges) -> KeyRanges:
+    """Keys both masks show: lo = max, hi = min (e.g. a sliding window inside packed documents).
+    The maximum / minimum of non-decreasing sequences is non-decreasing, so the contract holds."""
+    if (a.batch, a.num_queries, a.num_keys) != (b.batch, b.num_queries, b.num_keys):
+        raise ValueError(f"cannot intersect key ranges of [B, Sq, Sk] = [{a.batch}, {a.num_queries}, {a.num_keys}] "
+                         f"and [{b.batch}, {b.num_queries}, {b.num_keys}]")
+    if a.device != b.device:
+        raise ValueError(f"cannot intersect key ranges on {a.device} and {b.device}")
+    return KeyRanges(torch.maximum(a.lo, b.lo), torch.minimum(a.hi, b.hi), a.num_keys)
+
+
 def positions_from_ranges(ranges: KeyRanges) -> torch.Tensor:
     """q - lo[q] (int32 [B, S]): positions that restart at every document start."""
     q = torch.arange(ranges.num_queries, device=ranges.lo.device, dtype=torch.int32)[None, :]

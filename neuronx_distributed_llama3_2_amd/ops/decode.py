@@ -18,19 +18,32 @@ from ._ext import ext, use_native
 CHUNK = 128
 
 
+def decode_window(window: Optional[int], num_keys: int) -> int:
+    """The window the decode kernels get: 0 (none) for None, 0 or a window of at least num_keys keys."""
+    if window is None:
+        return 0
+    window = int(window)
+    if window < 0:
+        raise ValueError(f"window must be positive, got {window}")
+    return 0 if window >= num_keys else window
+
+
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, seq_len: torch.Tensor,
                      cache_idx: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None,
-                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     out: Optional[torch.Tensor] = None, window: Optional[int] = None) -> torch.Tensor:
     """q: [B, T, Hq, D] new-token queries; keys [0, seq_len[b]) are valid for the LAST token, and
-    token t sees keys < seq_len[b] - (T - 1 - t).  Returns [B, T, Hq, D]."""
+    token t sees keys < lim = seq_len[b] - (T - 1 - t).  window: sliding-window attention, token t
+    sees only the keys >= lim - window (itself and the window - 1 before it); None, 0 or at least
+    the cache length mean no window.  Returns [B, T, Hq, D]."""
     B, T, Hq, D = q.shape
+    window = decode_window(window, k_cache.shape[2])
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
     if out is None:
         out = torch.empty((B, T, Hq, D), dtype=q.dtype, device=q.device)
     if use_native(q, k_cache):
         nsplit = max(1, (k_cache.shape[2] + CHUNK - 1) // CHUNK)
         ext().decode_attn(q, k_cache, v_cache, cache_idx.to(torch.int32) if cache_idx is not None else None,
-                          seq_len.to(torch.int32), out, float(scale), nsplit)
+                          seq_len.to(torch.int32), out, float(scale), nsplit, *((window,) if window else ()))
         return out
     Hkv = k_cache.shape[1]
     g = Hq // Hkv
@@ -43,8 +56,12 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
         s = torch.matmul(qq, kk.transpose(-1, -2)) * scale
         ti = torch.arange(T, device=q.device)[:, None]
         ki = torch.arange(L, device=q.device)[None, :]
-        s = s.masked_fill(ki >= (L - (T - 1 - ti)), float("-inf"))
-        p = torch.softmax(s, -1)
+        lim = L - (T - 1 - ti)
+        hidden = ki >= lim
+        if window:
+            hidden = hidden | (ki < lim - window)
+        s = s.masked_fill(hidden, float("-inf"))
+        p = torch.softmax(s, -1).nan_to_num(0.0)   # a row with no visible key (seq_len < T) is 0, as the kernels
         out[b] = torch.matmul(p, vv).permute(1, 0, 2).to(out.dtype)
     return out
 
