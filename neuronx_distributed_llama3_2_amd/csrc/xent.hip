@@ -40,20 +40,22 @@ __global__ void __launch_bounds__(256) stats_kernel(const T* __restrict__ logits
 #pragma unroll
     for (int j = 1; j < 8; ++j) lm = fmaxf(lm, f[j]);
     const float nm = fmaxf(m, lm);
+    // a -inf logit (masked column) contributes 0 and a thread that has only seen such columns keeps
+    // s = 0: with nm = -inf the plain exp(-inf - (-inf)) would be NaN.  NaN logits still propagate.
     float acc = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      acc += __expf(f[j] - nm);
+      acc += f[j] == -INFINITY ? 0.f : __expf(f[j] - nm);
       sx += f[j];
     }
-    s = s * __expf(m - nm) + acc;
+    s = s * (m == -INFINITY ? 0.f : __expf(m - nm)) + acc;
     m = nm;
   }
   for (int c = nvec * 8 + threadIdx.x; c < V; c += 256) {  // tail (V % 8)
     float f;
     if constexpr (sizeof(T) == 2) f = bf2f(((const uint16_t*)x)[c]); else f = ((const float*)x)[c];
     const float nm = fmaxf(m, f);
-    s = s * __expf(m - nm) + __expf(f - nm);
+    s = s * (m == -INFINITY ? 0.f : __expf(m - nm)) + (f == -INFINITY ? 0.f : __expf(f - nm));
     m = nm;
     sx += f;
   }
