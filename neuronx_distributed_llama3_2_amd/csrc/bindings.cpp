@@ -18,7 +18,7 @@ int flash_attn_fwd_launch(const void*, const void*, const void*, void*, float*, 
                           const int64_t*, const int64_t*, int, int, int, int, int, int, float, int, int,
                           const DropoutArgs&, const int*, const int*, hipStream_t);
 int64_t flash_attn_bwd_workspace(int, int, int, int, int, int, int, int);
-void flash_attn_bwd_set_knob(int, int);
+void flash_attn_bwd_set_chunk(int);
 int transpose_bf16_launch(const void*, void*, int64_t, int64_t, int64_t, int64_t, hipStream_t);
 void transpose_set_variant(int);
 int flash_attn_bwd_launch(const void*, const void*, const void*, const void*, const void*, const float*, float*,
@@ -197,7 +197,7 @@ void flash_attn_bwd(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::
   const int* q_lo_p = range_ptr(q_lo, "q_lo", B, Sk, q);
   const int* q_hi_p = range_ptr(q_hi, "q_hi", B, Sk, q);
   auto opts = q.options().dtype(at::kFloat);
-  // fp32 workspace: dQ / dK / dV accumulators + per-row constants (sized by the kernel TU)
+  // fp32 workspace: dQ accumulator, per-row constants, per-item dK / dV slabs (laid out by the kernel TU)
   at::Tensor ws = at::empty({nxd::flash_attn_bwd_workspace(B, Sq, Sk, Hq, Hkv, D, causal ? 1 : 0, (int)causal_offset)}, opts);
   check_rc(nxd::flash_attn_bwd_launch(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
                                       lse.data_ptr<float>(), ws.data_ptr<float>(), dq.data_ptr(),
@@ -1155,8 +1155,11 @@ PYBIND11_MODULE(_C, m) {
         py::arg("lse"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("scale"), py::arg("causal"),
         py::arg("causal_offset"), py::arg("dropout_p") = 0.0, py::arg("seed") = 0, py::arg("head_offset") = 0,
         py::arg("lo") = py::none(), py::arg("hi") = py::none(), py::arg("q_lo") = py::none(), py::arg("q_hi") = py::none());
-  // A/B knobs of the backward: 0 = ablation flags, 1 = chunk override (0 = auto)
-  m.def("flash_attn_set_knob", [](int which, int value) { nxd::flash_attn_bwd_set_knob(which, value); });
+  // the backward's one override: knob 1 = work-item chunk length (0 = chosen per shape, -1 = re-read NXD_FAB_CHUNK)
+  m.def("flash_attn_set_knob", [](int which, int value) {
+    TORCH_CHECK(which == 1, "flash_attn_set_knob: the only knob is 1 (backward work-item chunk), got ", which);
+    nxd::flash_attn_bwd_set_chunk(value);
+  });
   m.def("rmsnorm_fwd", &rmsnorm_fwd);
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("transpose_set_variant", [](bool tr) { nxd::transpose_set_variant(tr ? 1 : 0); });

@@ -8,14 +8,17 @@
 //     space.  GQA reduction of dK/dV happens in registers — no repeat_kv, no second pass.
 //   * Work items = (key block, chunk): the host sizes chunks so there are >= 2 items per CU even
 //     at TP=8 head counts (one kv head per GPU), and the causal triangle is cut into near-equal
-//     pieces instead of one workgroup per key block whose runtime is the longest sweep.  Items
-//     of one key block write their dK/dV partials (256 KiB per item) with plain stores into
-//     per-item slabs that the bf16 convert pass sums (f32 atomics into one accumulator: knob 5).
+//     pieces instead of one workgroup per key block whose runtime is the longest sweep.  Every
+//     item writes its dK/dV partials (256 KiB at D=128) with plain stores into a slab of its own;
+//     the bf16 convert pass sums the slabs of a key block in item order, so dK/dV are bitwise
+//     repeatable and cost no atomics (profiles/r3_fab_slab_ab.jsonl: 2.117 -> 2.008 ms at 32/8
+//     heads against f32 atomics into one accumulator).  Work items run in dispatch order, so
+//     consecutive items land on different XCDs and every XCD gets the same mix of heavy and
+//     light items (profiles/r2_fab_xcd_map_ab.jsonl).
 //   * "key on the lane": S = Q K^T and dP = dO V^T put the key on the MFMA column, so their
 //     fp32 accumulators convert in place into the A operands of dV += P^T dO and dK += dS^T Q
 //     (accumulator-as-operand: no LDS round trip for P / dS), and the dV / dK accumulators come
-//     out [key][d] with d on the lane — the full-rate shape for the f32 atomics (two 128-B row
-//     segments per wave-instruction).
+//     out [key][d] with d on the lane: two full 128-B row segments per store instruction.
 //   * row constants as initial accumulators: S starts at -LSE/scale and dP at -delta, so
 //     P = exp2(scale*log2e * S) and dS = P * dP need no per-element subtraction;
 //   * K of the block lives in LDS (row reads for S, transposed reads for dQ); V rows live in
@@ -25,12 +28,15 @@
 //     block's 256 keys (D=128; D=64 splits keys in halves and sums the halves in LDS) and adds
 //     it with f32 atomics into an fp32 dQ accumulator.  At 256 keys per block the atomic volume
 //     is one byte per 640 FLOPs (half of a 128-key design).  At S=8192, 32/8 heads that is 2.21 GB
-//     of dQ adds + 0.55 GB of dK/dV adds; at the chip-wide f32 atomic rate (~1.3 TB/s, any adder
-//     placement) that alone is ~2.1 ms, the kernel's time (profiles/r2_fab_ablate_after.jsonl: the
-//     body with every atomic ablated runs 1.59 ms).  Going lower needs fewer atomic BYTES, not a
-//     faster body: 256 keys per workgroup is the register-file maximum for resident dK/dV
-//     (256 keys x 128 d x 2 x 4 B = half of a CU's 512 KiB of registers).
-#include "gemm_tile.h"
+//     of dQ adds; at the chip-wide f32 atomic rate (~1.3 TB/s, any adder placement) they bound
+//     the kernel (profiles/r2_fab_ablate_after.jsonl: the body without any atomic ran 1.59 ms).
+//     Going lower needs fewer atomic BYTES, not a faster body: 256 keys per workgroup is the
+//     register-file maximum for resident dK/dV (256 keys x 128 d x 2 x 4 B = half of a CU's
+//     512 KiB of registers).
+//   * Pipeline depths are fixed at what won (profiles/r2_fab_pipeline_ab_v2_interleave.jsonl).
+//     The only tuning override left is the chunk length (NXD_FAB_CHUNK / flash_attn_set_knob(1, n)),
+//     which changes the item plan and nothing about the arithmetic.
+#include "attn_tile.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -47,7 +53,25 @@ constexpr int kWaves = 4;
 constexpr int kThreads = 256;
 constexpr int kBlockK = 256;  // keys per key block (64 per wave)
 constexpr int kBlockQ = 32;   // query rows per tile
-constexpr int kPipeDq = 3;    // dQ operand reads ahead (one MFMA per step)
+// operand reads issued this many steps ahead of their MFMAs
+constexpr int kPipe = 1;      // S / dP
+constexpr int kPipeDvDk = 2;  // dV / dK transposed reads (the first ones go out before the softmax VALU)
+constexpr int kPipeDq = 3;    // dQ (one MFMA per step)
+
+// dynamic LDS of bwd_kernel<D>: byte offsets of its images and their total
+template <int D>
+struct Lds {
+  static constexpr int KV_BYTES = kBlockK * D * 2;
+  static constexpr int QT_BYTES = kBlockQ * D * 2;
+  static constexpr int OFF_K = 0;                            // K block image
+  static constexpr int OFF_Q = KV_BYTES;                     // 2 buffers
+  static constexpr int OFF_DO = OFF_Q + 2 * QT_BYTES;        // 2 buffers
+  static constexpr int OFF_DS = OFF_DO + 2 * QT_BYTES;       // 256 x 64 B
+  static constexpr int OFF_LD = OFF_DS + kBlockK * 64;       // 2 buffers x (32 nlse + 32 ndelta) floats
+  static constexpr int OFF_RED = OFF_LD + 512;               // D=64: dQ key-half partials (2 x 4 KiB)
+  static constexpr int OFF_V = OFF_RED + (D == 64 ? 8192 : 0);  // V rows of every wave's 2nd key column
+  static constexpr int BYTES = OFF_V + KV_BYTES / 2;
+};
 
 struct BwdParams {
   const uint16_t* q;
@@ -57,9 +81,7 @@ struct BwdParams {
   const float* nlse;    // [B, Hq, Sq]: -LSE / scale  (-inf for empty rows)
   const float* ndelta;  // [B, Hq, Sq]: -rowsum(dO * O)
   float* dq_acc;        // [B, Hq, Sq_pad, D] fp32, zero-initialised
-  float* dk_acc;        // [B, Hkv, Sk_pad, D] fp32, zero-initialised
-  float* dv_acc;        // [B, Hkv, Sk_pad, D] fp32, zero-initialised
-  float* dk_slab;       // slab mode (non-null): [B*Hkv, items per bh, kBlockK, D] fp32 per-item partials,
+  float* dk_slab;       // [B*Hkv, items per bh, kBlockK, D] fp32 per-item partials,
   float* dv_slab;       //   plain stores (no atomics), summed by slab_convert_kernel
   int64_t q_sb, q_ss, q_sh;
   int64_t k_sb, k_ss, k_sh;
@@ -70,10 +92,6 @@ struct BwdParams {
   int causal;
   int causal_offset;
   int chunk;   // max (q head, q tile) iterations per work item
-  int xcd_map; // 0: contiguous item ranges per XCD, 2: interleaved (see bwd_kernel)
-  int ablate;  // timing-only ablations (NXD_FAB_ABLATE; outputs wrong): 1 no dQ atomics,
-               // 2 no dK/dV atomics, 16 no Q/dO tile loads,
-               // 32 no per-tile barriers
   DropoutArgs drop;  // DROP variants only
   // RANGE variants only: key k of batch row b is seen by the queries [rq_lo[b, k], rq_hi[b, k])
   // (int32 [B, Sk], each non-decreasing along k: the transposed form of the forward's per-query
@@ -89,27 +107,6 @@ __host__ __device__ inline int kb_iters(int kb, int Sq, int G, int causal, int o
   qstart = (qstart / kBlockQ) * kBlockQ;
   const int n_qt = qstart < Sq ? (Sq - qstart + kBlockQ - 1) / kBlockQ : 0;
   return G * n_qt;
-}
-
-template <int D>
-__device__ __forceinline__ int swz(int row, int ch) {
-  if constexpr (D == 128) {
-    return ch ^ (((row & 3) << 2) | ((row >> 2) & 3));
-  } else {
-    return ch ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3));
-  }
-}
-template <int D>
-__device__ __forceinline__ int lds_off(int row, int ch) {
-  return row * (D * 2) + swz<D>(row, ch) * 16;
-}
-
-typedef __attribute__((address_space(3))) short4_t* lds_s4_t;
-
-// transposed read of 4 consecutive rows at (row0 + tq, col .. col+3) of a swizzled [rows][D] image
-template <int D>
-__device__ __forceinline__ short4_t tr_read(const char* base, int row, int col) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)(base + lds_off<D>(row, col >> 3) + (col & 7) * 2));
 }
 
 // dS^T image: [256 keys][32 q] bf16, 64-B rows, 8-B chunks XOR-swizzled by (row & 7)
@@ -129,7 +126,7 @@ __device__ __forceinline__ void lds_st(uint32_t a, const T& v) {
   *(__attribute__((address_space(3))) T*)(uintptr_t)a = v;
 }
 __device__ __forceinline__ short4_t lds_tr(uint32_t a) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t)(uintptr_t)a);
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4_t*)(uintptr_t)a);
 }
 
 // acc += A * B with the accumulator pinned to AGPRs.  The 256 resident dK/dV accumulators must
@@ -145,8 +142,6 @@ __device__ __forceinline__ void mfma_acc_agpr(f32x16_t& acc, const TA& a, const 
   asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
 }
 
-// PIPE: S / dP operand reads issued this many steps ahead of their MFMAs; PIPE_DVDK: the same for
-// the dV / dK transposed reads (the first ones go out before the softmax VALU).
 // DROP: attention dropout (reference NKI flash_attn_bwd dropout_p / seed): the forward's keep mask m
 // (0 or 1/(1-p)) is regenerated from the hash; dV uses P*m, dS = P * (m * dO.V^T - delta), so dP
 // starts at 0 instead of -delta and delta is re-read from the tile's LDS row constants.
@@ -154,23 +149,14 @@ __device__ __forceinline__ void mfma_acc_agpr(f32x16_t& acc, const TA& a, const 
 // (host plan, workspace and slab layout untouched); inside the kernel the block's query tiles are
 // restricted to [q_lo of its first key, q_hi of its last key) and that smaller (q head x q tile)
 // space is split over the same items -- items left with nothing take the empty-item path.
-template <int D, int PIPE, int PIPE_DVDK, bool DROP, bool RANGE = false>
+template <int D, bool DROP, bool RANGE>
 __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
-  constexpr int kPipe = PIPE;
+  using I = Lds<D>;
   constexpr int CH = D / 8;
   constexpr int KS = D / 16;
   constexpr int NDB = D / 32;
-  constexpr int KV_BYTES = kBlockK * D * 2;
-  constexpr int QT_BYTES = kBlockQ * D * 2;
-  constexpr int OFF_K = 0;                            // K block image
-  constexpr int OFF_Q = KV_BYTES;                     // 2 buffers
-  constexpr int OFF_DO = OFF_Q + 2 * QT_BYTES;        // 2 buffers
-  constexpr int OFF_DS = OFF_DO + 2 * QT_BYTES;       // 256 x 64 B
-  constexpr int OFF_LD = OFF_DS + kBlockK * 64;       // 2 buffers x (32 nlse + 32 ndelta) floats
-  constexpr int OFF_RED = OFF_LD + 512;               // D=64: dQ key-half partials (2 x 4 KiB)
-  constexpr int OFF_V = OFF_RED + (NDB == 2 ? 8192 : 0);  // V rows of every wave's 2nd key column
   constexpr int ROWS_PER_PIECE = 1024 / (2 * D);
-  constexpr int QT_PIECES = QT_BYTES / 1024;
+  constexpr int QT_PIECES = I::QT_BYTES / 1024;
   constexpr int QT_PIECES_PER_WAVE = QT_PIECES / kWaves;
   constexpr int KEY_SPLIT = kWaves / NDB;             // 1 (D=128) or 2 (D=64)
   constexpr int KEYS_PER_DQ = kBlockK / KEY_SPLIT;
@@ -179,13 +165,10 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
 
   const int G = p.Hq / p.Hkv;
   const int BH = p.B * p.Hkv;
-  // work-item order = dispatch order (xcd_map 2: consecutive items on different XCDs, so every XCD
-  // gets the same mix of heavy and light items) or contiguous item ranges per XCD (0, round 1: the
-  // first XCD received all of the heaviest key blocks' items)
-  const int L = p.xcd_map == 2 ? (int)blockIdx.x : xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = L % BH;
-  int kc = L / BH;
-  const int64_t slab = (int64_t)bh * (gridDim.x / BH) + kc;  // this item's dK/dV slab (slab mode)
+  // work-item order = dispatch order
+  const int bh = blockIdx.x % BH;
+  int kc = blockIdx.x / BH;
+  const int64_t slab = (int64_t)bh * (gridDim.x / BH) + kc;  // this item's dK/dV slab
   // ---- decode (key block, chunk) of this work item: key blocks in order (heaviest first)
   const int nkb = (p.Sk + kBlockK - 1) / kBlockK;
   int kb = 0, it_begin = 0, it_end = 0;
@@ -214,18 +197,15 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
     kc -= nc;
   }
   if (kb >= nkb || it_begin >= it_end) {  // (host sizes the grid exactly; defensive)
-    if (p.dk_slab != nullptr) {  // an empty item's slab still enters the sum
-      for (int i = threadIdx.x; i < kBlockK * D; i += kThreads) {
-        p.dk_slab[slab * kBlockK * D + i] = 0.f;
-        p.dv_slab[slab * kBlockK * D + i] = 0.f;
-      }
+    for (int i = threadIdx.x; i < kBlockK * D; i += kThreads) {  // an empty item's slab still enters the sum
+      p.dk_slab[slab * kBlockK * D + i] = 0.f;
+      p.dv_slab[slab * kBlockK * D + i] = 0.f;
     }
     return;
   }
 
   const int b = bh / p.Hkv, hkv = bh % p.Hkv;
   const int Sq_pad = (p.Sq + kBlockQ - 1) / kBlockQ * kBlockQ;
-  const int Sk_pad = nkb * kBlockK;
   int qstart = 0;
   if (p.causal) qstart = max(0, kb * kBlockK - p.causal_offset);
   qstart = (qstart / kBlockQ) * kBlockQ;
@@ -265,7 +245,7 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
     const int key = kb0 + row;
     u32x4_t kv4 = {0, 0, 0, 0};
     if (key < p.Sk) kv4 = *reinterpret_cast<const u32x4_t*>(kbase + (int64_t)key * p.k_ss + ch * 8);
-    *reinterpret_cast<u32x4_t*>(smem + OFF_K + lds_off<D>(row, ch)) = kv4;
+    *reinterpret_cast<u32x4_t*>(smem + I::OFF_K + lds_off<D>(row, ch)) = kv4;
   }
   // V rows: first key column in VGPRs, second in an LDS image (the 256 dK/dV accumulators
   // leave room for only one column of V in registers)
@@ -281,7 +261,7 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
       if (c == 0)
         vf[s] = __builtin_bit_cast(bf16x8_t, cv);
       else
-        *reinterpret_cast<u32x4_t*>(smem + OFF_V + lds_off<D>(32 * w + r, 2 * s + hh)) = cv;
+        *reinterpret_cast<u32x4_t*>(smem + I::OFF_V + lds_off<D>(32 * w + r, 2 * s + hh)) = cv;
     }
   }
 
@@ -297,15 +277,15 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
   // away; K / V a wave-uniform SGPR away, added per read so the registers are not replicated)
   uint32_t a_q[KS];
   uint32_t a_trq[2][NDB];                  // tr reads rows 4hh+tq+8j, col 32dbk+16(g&1)+4tp (Q; dO +const)
-  const uint32_t kofs0 = __builtin_amdgcn_readfirstlane((uint32_t)(OFF_K - OFF_Q + 64 * w * (2 * D)));
-  const uint32_t vofs0 = __builtin_amdgcn_readfirstlane((uint32_t)(OFF_V - OFF_Q + 32 * w * (2 * D)));
-  constexpr int DO_Q = OFF_DO - OFF_Q;
+  const uint32_t kofs0 = __builtin_amdgcn_readfirstlane((uint32_t)(I::OFF_K - I::OFF_Q + 64 * w * (2 * D)));
+  const uint32_t vofs0 = __builtin_amdgcn_readfirstlane((uint32_t)(I::OFF_V - I::OFF_Q + 32 * w * (2 * D)));
+  constexpr int DO_Q = I::OFF_DO - I::OFF_Q;
   uint32_t a_dsw[4];                       // dS^T writes: key 64w+r, q 8gq+4hh
   uint32_t a_dsr[2], a_ktr[2];             // dQ tr reads: dS^T keys kr0+8hh+tq+4j / K rows
 #pragma unroll
   for (int s = 0; s < KS; ++s) {
     const int a_row = lds_off<D>(r, 2 * s + hh);
-    a_q[s] = L0 + OFF_Q + a_row;
+    a_q[s] = L0 + I::OFF_Q + a_row;
   }
 #pragma unroll
   for (int j = 0; j < 2; ++j)
@@ -313,17 +293,17 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
     for (int dbk = 0; dbk < NDB; ++dbk) {
       const int col = 32 * dbk + 16 * (g & 1) + 4 * tp;
       const int a_tr = lds_off<D>(4 * hh + tq + 8 * j, col >> 3) + (col & 7) * 2;
-      a_trq[j][dbk] = L0 + OFF_Q + a_tr;
+      a_trq[j][dbk] = L0 + I::OFF_Q + a_tr;
     }
 #pragma unroll
-  for (int gq = 0; gq < 4; ++gq) a_dsw[gq] = L0 + OFF_DS + 64 * w * 64 + ds_off(r, 8 * gq + 4 * hh);
+  for (int gq = 0; gq < 4; ++gq) a_dsw[gq] = L0 + I::OFF_DS + 64 * w * 64 + ds_off(r, 8 * gq + 4 * hh);
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    a_dsr[j] = L0 + OFF_DS + kr0 * 64 + ds_off(8 * hh + tq + 4 * j, 16 * (g & 1) + 4 * tp);
+    a_dsr[j] = L0 + I::OFF_DS + kr0 * 64 + ds_off(8 * hh + tq + 4 * j, 16 * (g & 1) + 4 * tp);
     const int col = 32 * dbq + 16 * (g & 1) + 4 * tp;
-    a_ktr[j] = L0 + OFF_K + kr0 * (2 * D) + lds_off<D>(8 * hh + tq + 4 * j, col >> 3) + (col & 7) * 2;
+    a_ktr[j] = L0 + I::OFF_K + kr0 * (2 * D) + lds_off<D>(8 * hh + tq + 4 * j, col >> 3) + (col & 7) * 2;
   }
-  uint32_t a_ld = L0 + OFF_LD + 16 * hh;  // nlse / ndelta rows 8gq + 4hh
+  uint32_t a_ld = L0 + I::OFF_LD + 16 * hh;  // nlse / ndelta rows 8gq + 4hh
   // opaque: otherwise the compiler re-splits each base into (lane part + big constant) and puts the
   // v_add back into the loop (the big constants do not fit the 16-bit ds offset)
 #pragma unroll
@@ -378,13 +358,13 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
         qo = rr * (int)p.q_ss + ch * 8;
         dof = rr * (int)p.do_ss + ch * 8;
       }
-      dma16(qb + qo, __builtin_amdgcn_readfirstlane(L0 + OFF_Q + buf * QT_BYTES + piece * 1024));
-      dma16(db + dof, __builtin_amdgcn_readfirstlane(L0 + OFF_DO + buf * QT_BYTES + piece * 1024));
+      dma16(qb + qo, __builtin_amdgcn_readfirstlane(L0 + I::OFF_Q + buf * I::QT_BYTES + piece * 1024));
+      dma16(db + dof, __builtin_amdgcn_readfirstlane(L0 + I::OFF_DO + buf * I::QT_BYTES + piece * 1024));
     }
     if (w == 0) {
       const int qi = min(qt0 + (lane & 31), p.Sq - 1);
       const float* src = (lane < 32 ? p.nlse : p.ndelta) + ((int64_t)b * p.Hq + hq) * p.Sq + qi;
-      dma4(src, __builtin_amdgcn_readfirstlane(L0 + OFF_LD + buf * 256));
+      dma4(src, __builtin_amdgcn_readfirstlane(L0 + I::OFF_LD + buf * 256));
     }
   };
 
@@ -396,7 +376,6 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
       acc_dk[c][i] = f32x16_t{0};
       acc_dv[c][i] = f32x16_t{0};
     }
-  bool touched[2] = {false, false};
 
   issue_tile(it_begin, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -405,14 +384,13 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
   // one tile; BUF (0/1) is a compile-time constant so every LDS offset folds into the instruction
   auto tile = [&](auto BUFC, int it) {
     constexpr int buf = decltype(BUFC)::value;
-    constexpr int QB = buf * QT_BYTES, DB = buf * QT_BYTES, LB = buf * 256;  // offsets from the per-lane bases
+    constexpr int QB = buf * I::QT_BYTES, DB = buf * I::QT_BYTES, LB = buf * 256;  // offsets from the per-lane bases
     const int hq = hkv * G + it / n_qt;
     const int qt0 = qstart + (it % n_qt) * kBlockQ;
     // buffer buf^1 was last read in the previous tile, closed by its final barrier
-    if (it + 1 < it_end && !(p.ablate & 16)) issue_tile(it + 1, buf ^ 1);
+    if (it + 1 < it_end) issue_tile(it + 1, buf ^ 1);
     uint32_t kofs = kofs0, vofs = vofs0;
     asm volatile("" : "+s"(kofs), "+s"(vofs));  // per tile: the adds stay next to their reads
-    const int qlast = qt0 + kBlockQ - 1 + p.causal_offset;  // last key any row of the tile may see
 
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -420,7 +398,6 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
       // no branch on the causal diagonal: a fully masked column computes P = dS = 0 (the tile's
       // time is set by wave 0, whose columns are never fully masked), and a branch around MFMAs
       // would need to be a uniform jump -- an MFMA ignores EXEC
-      touched[c] = touched[c] || !p.causal || kc0 <= qlast;
       {
         // ---- S = Q K^T - LSE/scale, dP = dO V^T - delta  (key on the lane; row constants as
         // the initial accumulators)
@@ -469,7 +446,7 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
           tr_hi[st][1] = lds_tr(a_trq[1][dbk] + QB + o);
         };
 #pragma unroll
-        for (int st = 0; st < PIPE_DVDK; ++st) ld_dvdk(st);
+        for (int st = 0; st < kPipeDvDk; ++st) ld_dvdk(st);
         __builtin_amdgcn_sched_barrier(0);
         // ---- P, dS (element e of the lane: query row 8(e>>2) + 4hh + (e&3), key kc0 + r).  Rows
         // 0-15 (half 0) first; the exps of half 1 run in the shadow of half 0's dV / dK MFMAs.
@@ -523,7 +500,7 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
 #pragma unroll
         for (int st = 0; st < 2 * NDB; ++st) {
           {
-            if (st + PIPE_DVDK < 2 * NDB) ld_dvdk(st + PIPE_DVDK);
+            if (st + kPipeDvDk < 2 * NDB) ld_dvdk(st + kPipeDvDk);
             const int s2 = st / NDB, dbk = st % NDB;
             const bf16s8_t db8 = {tr_lo[st][0][0], tr_lo[st][0][1], tr_lo[st][0][2], tr_lo[st][0][3],
                                   tr_hi[st][0][0], tr_hi[st][0][1], tr_hi[st][0][2], tr_hi[st][0][3]};
@@ -547,7 +524,7 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
     }
     // dS^T complete.  Raw barrier: the tile prefetch (LDS-DMA) stays in flight across it.
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (!(p.ablate & 32)) __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_s_barrier();
 
     // ---- dQ[q][d] += dS[q][key] K[key][d] over this wave's (d block, key range)
     // all key groups, masked ones included (their dS^T entries are zeros): unguarded MFMAs, and
@@ -577,10 +554,10 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
       __builtin_amdgcn_sched_barrier(0);
     }
     acc_dq += acc_dq2;
-    bool adder = !(p.ablate & 1);
+    bool adder = true;
     if constexpr (KEY_SPLIT == 2) {
       // key-half 1 hands its partial to key-half 0 through LDS (no doubled atomics)
-      float* red = reinterpret_cast<float*>(smem + OFF_RED) + (dbq * 64 + lane) * 16;
+      float* red = reinterpret_cast<float*>(smem + I::OFF_RED) + (dbq * 64 + lane) * 16;
       if (w >= NDB) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -609,7 +586,7 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
     } else {
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     }
-    if (!(p.ablate & 32)) __builtin_amdgcn_s_barrier();  // dS^T / Q / dO reads done; next tile landed
+    __builtin_amdgcn_s_barrier();  // dS^T / Q / dO reads done; next tile landed
   };
 
   for (int it = it_begin; it < it_end; it += 2) {
@@ -620,51 +597,25 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
   // the dK/dV MFMAs are inline asm (invisible to the hazard recognizer): give the last ones their
   // pass latency before the accumulators are read
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-  if (p.dk_slab != nullptr) {
-    // slab mode: this item's dK / dV partials -> its own slab with plain stores (every column,
-    // untouched ones as zeros; the accumulators of a fully masked column stay 0)
-    if (p.ablate & 2) return;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int64_t srow0 = slab * kBlockK + 64 * w + 32 * c;
-#pragma unroll
-      for (int dbk = 0; dbk < NDB; ++dbk) {
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-          int64_t off = (srow0 + 8 * gq + 4 * hh) * D + 32 * dbk + r;
-          asm volatile("" : "+v"(off));
-          float* dkr = p.dk_slab + off;
-          float* dvr = p.dv_slab + off;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            dkr[i * D] = acc_dk[c][dbk][4 * gq + i];
-            dvr[i * D] = acc_dv[c][dbk][4 * gq + i];
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-    return;
-  }
-  // ---- dK, dV partials -> fp32 workspace: C rows = key, col = d (d on the lane)
+  // ---- this item's dK / dV partials -> its own slab with plain stores: rows = key, col = d (d on
+  // the lane); every column is written (the accumulators of a fully masked column stay 0)
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
-    if (!touched[c] || (p.ablate & 2)) continue;
-    const int64_t krow0 = ((int64_t)b * p.Hkv + hkv) * Sk_pad + wkey0 + 32 * c;
+    const int64_t srow0 = slab * kBlockK + 64 * w + 32 * c;
 #pragma unroll
     for (int dbk = 0; dbk < NDB; ++dbk) {
       // one opaque row base per group of 4 rows, issued group by group: unconstrained, the
-      // scheduler precomputes all 256 64-bit atomic addresses next to the 256 live accumulators
+      // scheduler precomputes all 256 64-bit store addresses next to the 256 live accumulators
 #pragma unroll
       for (int gq = 0; gq < 4; ++gq) {
-        int64_t off = (krow0 + 8 * gq + 4 * hh) * D + 32 * dbk + r;
+        int64_t off = (srow0 + 8 * gq + 4 * hh) * D + 32 * dbk + r;
         asm volatile("" : "+v"(off));
-        float* dkr = p.dk_acc + off;
-        float* dvr = p.dv_acc + off;
+        float* dkr = p.dk_slab + off;
+        float* dvr = p.dv_slab + off;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          atomicAdd(dkr + i * D, acc_dk[c][dbk][4 * gq + i]);
-          atomicAdd(dvr + i * D, acc_dv[c][dbk][4 * gq + i]);
+          dkr[i * D] = acc_dk[c][dbk][4 * gq + i];
+          dvr[i * D] = acc_dv[c][dbk][4 * gq + i];
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -676,8 +627,7 @@ __global__ void __launch_bounds__(kThreads, 1) bwd_kernel(BwdParams p) {
 template <int D>
 __global__ void __launch_bounds__(256) prep_kernel(const uint16_t* o, const uint16_t* dout, const float* lse, float* nlse,
                                                   float* ndelta, int64_t o_sb, int64_t o_ss, int64_t o_sh, int64_t d_sb,
-                                                  int64_t d_ss, int64_t d_sh, int B, int Sq, int Hq, float inv_scale,
-                                                  float* dq_zero, int Sq_pad) {
+                                                  int64_t d_ss, int64_t d_sh, int B, int Sq, int Hq, float inv_scale) {
   constexpr int LPR = D / 8;
   const int64_t row = ((int64_t)blockIdx.x * 256 + threadIdx.x) / LPR;
   const int c = threadIdx.x % LPR;
@@ -687,11 +637,6 @@ __global__ void __launch_bounds__(256) prep_kernel(const uint16_t* o, const uint
     const int b = row / ((int64_t)Hq * Sq);
     const int h = (row / Sq) % Hq;
     const int qi = row % Sq;
-    if (dq_zero != nullptr) {   // this row's slice of the fp32 dQ accumulator (rows >= Sq are never read)
-      float* z = dq_zero + (((int64_t)b * Hq + h) * Sq_pad + qi) * D + c * 8;
-      *reinterpret_cast<f32x4_t*>(z) = f32x4_t{0.f, 0.f, 0.f, 0.f};
-      *reinterpret_cast<f32x4_t*>(z + 4) = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    }
     const u32x4_t ov = *reinterpret_cast<const u32x4_t*>(o + b * o_sb + (int64_t)qi * o_ss + h * o_sh + c * 8);
     const u32x4_t dv = *reinterpret_cast<const u32x4_t*>(dout + b * d_sb + (int64_t)qi * d_ss + h * d_sh + c * 8);
     float of[8], df[8];
@@ -729,7 +674,7 @@ __global__ void __launch_bounds__(256) acc_convert_kernel(const float* acc, uint
   *reinterpret_cast<u32x4_t*>(out + b * sb + (int64_t)si * ss + h * sh + c * 8) = pack8(f);
 }
 
-// slab mode: out (bf16, strided [B,S,H,D]) = scale * sum of the per-item partials of the row's
+// out (bf16, strided [B,S,H,D]) = scale * sum of the per-item partials of the row's
 // key block (items of key block kb of one (b, h) are slabs [pre(kb), pre(kb) + nc(kb)) of that
 // (b, h): the kernel's item numbering)
 template <int D>
@@ -848,23 +793,20 @@ int choose_chunk(int nkb, int Sq, int G, int causal, int off, int BH, int ncu) {
   return best;
 }
 
-// tuning knobs, resolved once at load (NXD_FAB_ABLATE / NXD_FAB_CHUNK) and settable from Python
-// (flash_attn_set_knob) for in-process A/B — no per-launch getenv
-static int g_ablate = -1, g_chunk = -1, g_xcd = -1;
-int xcd_map_mode() {
-  if (g_xcd < 0) {
-    const char* e = getenv("NXD_FAB_XCD_MAP");
-    g_xcd = e ? atoi(e) : 2;
+template <int D, bool DROP, bool RANGE>
+void launch_bwd(const BwdParams& p, int64_t items, hipStream_t stream) {
+  static bool attr_set = false;  // > 64 KiB of dynamic LDS must be opted into once per instantiation
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)bwd_kernel<D, DROP, RANGE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              Lds<D>::BYTES);
+    attr_set = true;
   }
-  return g_xcd;
+  hipLaunchKernelGGL((bwd_kernel<D, DROP, RANGE>), dim3((unsigned)items), dim3(kThreads), Lds<D>::BYTES, stream, p);
 }
-int ablate_flags() {
-  if (g_ablate < 0) {
-    const char* e = getenv("NXD_FAB_ABLATE");
-    g_ablate = e ? atoi(e) : 0;
-  }
-  return g_ablate;
-}
+
+// work-item chunk length override for tests and A/B tools (0 = choose_chunk): NXD_FAB_CHUNK, read
+// once, or flash_attn_set_knob(1, n) from Python -- no per-launch getenv
+static int g_chunk = -1;
 int chunk_override() {
   if (g_chunk < 0) {
     const char* e = getenv("NXD_FAB_CHUNK");
@@ -873,77 +815,71 @@ int chunk_override() {
   return g_chunk;
 }
 
-// dK/dV reduction across the items of a key block: 0 = f32 atomics into one accumulator, 1 = per-item
-// slabs written with plain stores and summed by the convert pass (NXD_FAB_DKV_SLAB, default 1).
-// Slabs take the 0.55 GB of dK/dV adds (S=8192, 32/8 heads) off the chip-wide f32 atomic rate the
-// kernel is bound by, for 0.55 GB of plain stores plus one read in the convert: 2.117 -> 2.008 ms
-// (32/8 heads), 1.072 -> 1.014 (TP=8 shape, B=4), 0.299 -> 0.275 (4/1, B=1); D=64 16/4 neutral
-// (profiles/r3_fab_slab_ab.jsonl).
-static int g_slab = -1;
-int slab_mode() {
-  if (g_slab < 0) {
-    const char* e = getenv("NXD_FAB_DKV_SLAB");
-    g_slab = e ? atoi(e) : 1;
-  }
-  return g_slab;
-}
-
-static int g_pipe = -1;
-int pipe_variant() {
-  if (g_pipe < 0) {
-    const char* e = getenv("NXD_FAB_PIPE");
-    g_pipe = e ? atoi(e) : 12;
-  }
-  return g_pipe;
-}
-
-template <int D, int PIPE, int PIPE_DVDK, bool DROP = false, bool RANGE = false>
-void launch_bwd(const BwdParams& p, int64_t items, size_t lds, hipStream_t stream) {
-  static bool attr_set = false;  // > 64 KiB of dynamic LDS must be opted into once per instantiation
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)bwd_kernel<D, PIPE, PIPE_DVDK, DROP, RANGE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((bwd_kernel<D, PIPE, PIPE_DVDK, DROP, RANGE>), dim3((unsigned)items), dim3(kThreads), lds, stream, p);
-}
-
-}  // namespace fab
-
-void flash_attn_bwd_set_knob(int which, int value) {
-  if (which == 0) fab::g_ablate = value;
-  if (which == 1) fab::g_chunk = value;
-  if (which == 3) fab::g_xcd = value;
-  if (which == 4) fab::g_pipe = value;  // pipeline depths: 12 (default), 11, 21, 0
-  if (which == 5) fab::g_slab = value;  // dK/dV: 0 atomics, 1 per-item slabs
-}
-
-namespace fab {
-// work-item chunk length and items per (batch, kv head) of a launch (one definition for the
-// workspace sizing and the launch)
-void plan(int B, int Sq, int Sk, int Hq, int Hkv, int causal, int causal_offset, int* chunk, int64_t* per_bh) {
+// The item plan and the fp32 workspace of one call, in floats: dq_acc | nlse | ndelta | dk_slab |
+// dv_slab (one definition for the workspace sizing and the launch).  dq_acc is a multiple of
+// kBlockQ * D floats and the nlse / ndelta pair is rounded up to 4, so every region that is read
+// or written 16 bytes at a time starts 16-byte aligned.
+struct Plan {
+  int chunk;       // (q head x q tile) iterations per work item
+  int64_t per_bh;  // work items (= slabs) per (batch, kv head)
+  int64_t Sq_pad, nlse, ndelta, dk_slab, dv_slab, total;
+};
+Plan make_plan(int B, int Sq, int Sk, int Hq, int Hkv, int D, int causal, int causal_offset) {
   const int nkb = (Sk + kBlockK - 1) / kBlockK;
   const int G = Hq / Hkv;
-  *chunk = chunk_override() > 0 ? chunk_override() : choose_chunk(nkb, Sq, G, causal, causal_offset, B * Hkv, num_cus());
-  int64_t n = 0;
-  for (int kb = 0; kb < nkb; ++kb) n += (kb_iters(kb, Sq, G, causal, causal_offset) + *chunk - 1) / *chunk;
-  *per_bh = n;
+  Plan pl;
+  pl.chunk = chunk_override() > 0 ? chunk_override() : choose_chunk(nkb, Sq, G, causal, causal_offset, B * Hkv, num_cus());
+  pl.per_bh = 0;
+  for (int kb = 0; kb < nkb; ++kb) pl.per_bh += (kb_iters(kb, Sq, G, causal, causal_offset) + pl.chunk - 1) / pl.chunk;
+  const int64_t rows = (int64_t)B * Hq * Sq;
+  pl.Sq_pad = (Sq + kBlockQ - 1) / kBlockQ * kBlockQ;
+  pl.nlse = (int64_t)B * Hq * pl.Sq_pad * D;
+  pl.ndelta = pl.nlse + rows;
+  pl.dk_slab = pl.nlse + (2 * rows + 3) / 4 * 4;
+  pl.dv_slab = pl.dk_slab + (int64_t)B * Hkv * pl.per_bh * kBlockK * D;
+  pl.total = 2 * pl.dv_slab - pl.dk_slab;
+  return pl;
 }
+
+// prep -> kernel -> dQ convert -> dK / dV slab converts
+template <int D>
+int run(BwdParams p, const Plan& pl, float* ws, const void* o, const float* lse, const int64_t* os, void* dq, void* dk,
+        void* dv, const int64_t* dqs, const int64_t* dks, const int64_t* dvs, float softmax_scale, bool range,
+        hipStream_t stream) {
+  // the dQ accumulator is added into; the slabs are written whole by the kernel
+  (void)hipMemsetAsync(ws, 0, (size_t)pl.nlse * sizeof(float), stream);
+  const int64_t nrows = (int64_t)p.B * p.Hq * p.Sq;
+  const int rows_per_block = 256 / (D / 8);
+  const int gpre = (int)((nrows + rows_per_block - 1) / rows_per_block);
+  if (gpre > 0)
+    hipLaunchKernelGGL(prep_kernel<D>, dim3(gpre), dim3(256), 0, stream, (const uint16_t*)o, p.dout, lse, ws + pl.nlse,
+                       ws + pl.ndelta, os[0], os[1], os[2], p.do_sb, p.do_ss, p.do_sh, p.B, p.Sq, p.Hq, 1.f / softmax_scale);
+  const int64_t items = pl.per_bh * p.B * p.Hkv;
+  if (items > 0) {
+    if (range)
+      launch_bwd<D, false, true>(p, items, stream);
+    else if (p.drop.enabled())
+      launch_bwd<D, true, false>(p, items, stream);
+    else
+      launch_bwd<D, false, false>(p, items, stream);
+  }
+  const int G = p.Hq / p.Hkv;
+  launch_convert<D>(p.dq_acc, dq, dqs, p.B, p.Sq, (int)pl.Sq_pad, p.Hq, softmax_scale, stream);
+  launch_slab_convert<D>(p.dk_slab, dk, dks, p.B, p.Sk, p.Hkv, softmax_scale, p.Sq, G, p.causal, p.causal_offset, pl.chunk,
+                         (int)pl.per_bh, stream);
+  launch_slab_convert<D>(p.dv_slab, dv, dvs, p.B, p.Sk, p.Hkv, 1.f, p.Sq, G, p.causal, p.causal_offset, pl.chunk,
+                         (int)pl.per_bh, stream);
+  return (int)hipGetLastError();
+}
+
 }  // namespace fab
 
-// fp32 workspace floats the backward needs: dq_acc + dk_acc + dv_acc + nlse + ndelta (+ the dK / dV
-// slabs in slab mode)
+void flash_attn_bwd_set_chunk(int value) { fab::g_chunk = value; }
+
+// fp32 workspace floats the backward needs
 int64_t flash_attn_bwd_workspace(int B, int Sq, int Sk, int Hq, int Hkv, int D, int causal, int causal_offset) {
-  const int64_t Sq_pad = (Sq + fab::kBlockQ - 1) / fab::kBlockQ * fab::kBlockQ;
-  const int64_t Sk_pad = (Sk + fab::kBlockK - 1) / fab::kBlockK * fab::kBlockK;
-  int64_t n = (int64_t)B * Hq * Sq_pad * D + 2 * (int64_t)B * Hkv * Sk_pad * D + 2 * (int64_t)B * Hq * Sq;
-  if (fab::slab_mode() && Hkv > 0 && Hq % Hkv == 0) {
-    int chunk;
-    int64_t per_bh;
-    fab::plan(B, Sq, Sk, Hq, Hkv, causal, causal_offset, &chunk, &per_bh);
-    n += 2 * (int64_t)B * Hkv * per_bh * fab::kBlockK * D;
-  }
-  return n;
+  if (Hkv <= 0 || Hq % Hkv != 0) return 0;
+  return fab::make_plan(B, Sq, Sk, Hq, Hkv, D, causal, causal_offset).total;
 }
 
 int flash_attn_bwd_launch(const void* q, const void* k, const void* v, const void* o, const void* dout,
@@ -957,53 +893,12 @@ int flash_attn_bwd_launch(const void* q, const void* k, const void* v, const voi
   if (Hkv <= 0 || Hq % Hkv != 0 || (D != 64 && D != 128)) return -1;
   const bool range = range_q_lo != nullptr;
   if (range && (range_q_hi == nullptr || drop.enabled())) return -3;  // no RANGE + DROP instantiation
-  const int G = Hq / Hkv;
-  const int64_t Sq_pad = (Sq + kBlockQ - 1) / kBlockQ * kBlockQ;
-  const int nkb = (Sk + kBlockK - 1) / kBlockK;
-  const int64_t Sk_pad = (int64_t)nkb * kBlockK;
-  float* dq_acc = ws;
-  float* dk_acc = dq_acc + (int64_t)B * Hq * Sq_pad * D;
-  float* dv_acc = dk_acc + (int64_t)B * Hkv * Sk_pad * D;
-  float* nlse = dv_acc + (int64_t)B * Hkv * Sk_pad * D;
-  float* ndelta = nlse + (int64_t)B * Hq * Sq;
-  int chunk;
-  int64_t per_bh;
-  plan(B, Sq, Sk, Hq, Hkv, causal, causal_offset, &chunk, &per_bh);
-  const bool slabs = slab_mode() != 0;
-  float* dk_slab = slabs ? ndelta + (int64_t)B * Hq * Sq : nullptr;
-  float* dv_slab = slabs ? dk_slab + (int64_t)B * Hkv * per_bh * kBlockK * D : nullptr;
-  // zeroing: one memset for the accumulators (the slabs are written whole by the kernel), or, opt-in,
-  // the dQ rows zeroed by the prep kernel, which visits every (row, head) anyway
-  // NXD_FAB_PREP_ZERO=1 zeroes in the prep kernel instead of the memset launch: bench 3,006 / 3,016
-  // vs 2,999 / 3,007 ms per step with the memset (profiles/r4_fab_prep_zero_ab.txt), so off
-  static int prep_zero = -1;
-  if (prep_zero < 0) {
-    const char* e = getenv("NXD_FAB_PREP_ZERO");
-    prep_zero = e ? (atoi(e) != 0) : 0;
-  }
-  const bool pz = slabs && prep_zero;
-  if (!pz)
-    (void)hipMemsetAsync(ws, 0, (size_t)((int64_t)B * Hq * Sq_pad * D + (slabs ? 0 : 2 * (int64_t)B * Hkv * Sk_pad * D)) * sizeof(float), stream);
-  float* dq_zero = pz ? dq_acc : nullptr;
-
-  const int64_t nrows = (int64_t)B * Hq * Sq;
-  const int rows_per_block = 256 / (D / 8);
-  const int gpre = (int)((nrows + rows_per_block - 1) / rows_per_block);
-  if (gpre > 0) {
-    if (D == 128)
-      hipLaunchKernelGGL(prep_kernel<128>, dim3(gpre), dim3(256), 0, stream, (const uint16_t*)o, (const uint16_t*)dout, lse,
-                         nlse, ndelta, os[0], os[1], os[2], dos[0], dos[1], dos[2], B, Sq, Hq, 1.f / softmax_scale,
-                         dq_zero, (int)Sq_pad);
-    else
-      hipLaunchKernelGGL(prep_kernel<64>, dim3(gpre), dim3(256), 0, stream, (const uint16_t*)o, (const uint16_t*)dout, lse,
-                         nlse, ndelta, os[0], os[1], os[2], dos[0], dos[1], dos[2], B, Sq, Hq, 1.f / softmax_scale,
-                         dq_zero, (int)Sq_pad);
-  }
+  const Plan pl = make_plan(B, Sq, Sk, Hq, Hkv, D, causal, causal_offset);
 
   BwdParams p{};
   p.q = (const uint16_t*)q; p.k = (const uint16_t*)k; p.v = (const uint16_t*)v; p.dout = (const uint16_t*)dout;
-  p.nlse = nlse; p.ndelta = ndelta; p.dq_acc = dq_acc; p.dk_acc = dk_acc; p.dv_acc = dv_acc;
-  p.dk_slab = dk_slab; p.dv_slab = dv_slab;
+  p.nlse = ws + pl.nlse; p.ndelta = ws + pl.ndelta; p.dq_acc = ws;
+  p.dk_slab = ws + pl.dk_slab; p.dv_slab = ws + pl.dv_slab;
   p.q_sb = qs[0]; p.q_ss = qs[1]; p.q_sh = qs[2];
   p.k_sb = ks[0]; p.k_ss = ks[1]; p.k_sh = ks[2];
   p.v_sb = vs[0]; p.v_ss = vs[1]; p.v_sh = vs[2];
@@ -1011,57 +906,12 @@ int flash_attn_bwd_launch(const void* q, const void* k, const void* v, const voi
   p.B = B; p.Sq = Sq; p.Sk = Sk; p.Hq = Hq; p.Hkv = Hkv;
   p.scale_log2 = softmax_scale * 1.4426950408889634f;
   p.causal = causal; p.causal_offset = causal_offset;
-
-  p.chunk = chunk;
-  const int64_t items = per_bh * B * Hkv;
-  p.ablate = ablate_flags();
-  p.xcd_map = xcd_map_mode();
+  p.chunk = pl.chunk;
   p.drop = drop;
   p.rq_lo = range_q_lo;
   p.rq_hi = range_q_hi;
-  if (items > 0) {
-    if (D == 128) {
-      const size_t lds = kBlockK * 128 * 2 + 4 * kBlockQ * 128 * 2 + kBlockK * 64 + 512 + 128 * 128 * 2;
-      if (range) {
-        launch_bwd<128, 1, 2, false, true>(p, items, lds, stream);
-      } else if (drop.enabled()) {
-        launch_bwd<128, 1, 2, true>(p, items, lds, stream);
-      } else switch (pipe_variant()) {
-        case 11: launch_bwd<128, 1, 1>(p, items, lds, stream); break;
-        case 21: launch_bwd<128, 2, 1>(p, items, lds, stream); break;
-        case 0: launch_bwd<128, 0, 0>(p, items, lds, stream); break;
-        default: launch_bwd<128, 1, 2>(p, items, lds, stream); break;
-      }
-    } else {
-      const size_t lds = kBlockK * 64 * 2 + 4 * kBlockQ * 64 * 2 + kBlockK * 64 + 512 + 2 * 64 * 16 * 4 + 128 * 64 * 2;
-      if (range)
-        launch_bwd<64, 1, 2, false, true>(p, items, lds, stream);
-      else if (drop.enabled())
-        launch_bwd<64, 1, 2, true>(p, items, lds, stream);
-      else
-        launch_bwd<64, 1, 2>(p, items, lds, stream);
-    }
-  }
-  if (D == 128) {
-    launch_convert<128>(dq_acc, dq, dqs, B, Sq, (int)Sq_pad, Hq, softmax_scale, stream);
-    if (slabs) {
-      launch_slab_convert<128>(dk_slab, dk, dks, B, Sk, Hkv, softmax_scale, Sq, G, causal, causal_offset, chunk, (int)per_bh, stream);
-      launch_slab_convert<128>(dv_slab, dv, dvs, B, Sk, Hkv, 1.f, Sq, G, causal, causal_offset, chunk, (int)per_bh, stream);
-    } else {
-      launch_convert<128>(dk_acc, dk, dks, B, Sk, (int)Sk_pad, Hkv, softmax_scale, stream);
-      launch_convert<128>(dv_acc, dv, dvs, B, Sk, (int)Sk_pad, Hkv, 1.f, stream);
-    }
-  } else {
-    launch_convert<64>(dq_acc, dq, dqs, B, Sq, (int)Sq_pad, Hq, softmax_scale, stream);
-    if (slabs) {
-      launch_slab_convert<64>(dk_slab, dk, dks, B, Sk, Hkv, softmax_scale, Sq, G, causal, causal_offset, chunk, (int)per_bh, stream);
-      launch_slab_convert<64>(dv_slab, dv, dvs, B, Sk, Hkv, 1.f, Sq, G, causal, causal_offset, chunk, (int)per_bh, stream);
-    } else {
-      launch_convert<64>(dk_acc, dk, dks, B, Sk, (int)Sk_pad, Hkv, softmax_scale, stream);
-      launch_convert<64>(dv_acc, dv, dvs, B, Sk, (int)Sk_pad, Hkv, 1.f, stream);
-    }
-  }
-  return (int)hipGetLastError();
+  return D == 128 ? run<128>(p, pl, ws, o, lse, os, dq, dk, dv, dqs, dks, dvs, softmax_scale, range, stream)
+                  : run<64>(p, pl, ws, o, lse, os, dq, dk, dv, dqs, dks, dvs, softmax_scale, range, stream);
 }
 
 }  // namespace nxd

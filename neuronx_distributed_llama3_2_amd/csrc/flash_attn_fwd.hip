@@ -20,7 +20,7 @@
 //     (T1, shared L2), heavy causal q-blocks first.
 //   * arbitrary (batch, seq, head) strides, so Q/K/V can be read straight out of a fused
 //     [S, B, (Hq+2Hkv)*D] QKV projection output and O written into [S, B, Hq*D].
-#include "gemm_tile.h"
+#include "attn_tile.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -52,21 +52,6 @@ struct FwdParams {
   const int* rlo;
   const int* rhi;
 };
-
-// 16-byte chunk swizzle of a [rows][D] bf16 LDS image (D/8 chunks per row).
-template <int D>
-__device__ __forceinline__ int swz(int row, int ch) {
-  if constexpr (D == 128) {
-    return ch ^ (((row & 3) << 2) | ((row >> 2) & 3));
-  } else {
-    return ch ^ ((((row >> 1) & 1) << 2) | ((row >> 2) & 3));
-  }
-}
-
-template <int D>
-__device__ __forceinline__ int lds_off(int row, int ch) {  // byte offset of a 16-B chunk
-  return row * (D * 2) + swz<D>(row, ch) * 16;
-}
 
 // ds_read_b64_tr_b16 as inline asm: the builtin form makes the compiler put an s_waitcnt vmcnt(0)
 // (it cannot tell the read from the in-flight LDS-DMA of the next tile) in front of the first V

@@ -143,21 +143,17 @@ def test_cross_lengths_fwd_bwd():
     _check_bwd(q, k, v, kr, True, "cross")
 
 
-@pytest.mark.parametrize("slab", [0, 1])
-def test_backward_item_split(slab):
-    # many work items per key block (chunk 8), some left without tiles by the range restriction,
-    # dK/dV through atomics (0) and through per-item slabs (1)
+def test_backward_item_split():
+    # many work items per key block (chunk 8), some left without tiles by the range restriction
     B, S, Hq, Hkv, D = 1, 1024, 4, 1, 128
     q, k, v = _inputs(B, S, S, Hq, Hkv, D)
     kr = _doc_ranges([[0, 300, 301, 777, 1024]], S)
     ext = ops.ext()
     ext.flash_attn_set_knob(1, 8)
-    ext.flash_attn_set_knob(5, slab)
     try:
-        _check_bwd(q, k, v, kr, True, f"item split slab={slab}")
+        _check_bwd(q, k, v, kr, True, "item split")
     finally:
         ext.flash_attn_set_knob(1, -1)
-        ext.flash_attn_set_knob(5, -1)
 
 
 def test_forward_independence_bitwise():

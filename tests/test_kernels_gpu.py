@@ -106,24 +106,54 @@ def _bwd_check(B, Sq, Sk, Hq, Hkv, D, causal):
 @pytest.mark.parametrize("D", [64, 128])
 def test_flash_bwd_chunked_items(D):
     # one kv head (TP=8 head count): each 256-key block's query sweep is cut into several work
-    # items whose dK/dV partials meet in the fp32 atomics workspace
+    # items whose dK/dV partials meet in the convert pass, which sums their per-item fp32 slabs
     _bwd_check(1, 4096, 4096, 4, 1, D, True)
 
 
-@pytest.mark.parametrize("slab", [0, 1])
-def test_flash_bwd_dkdv_slab_mode(slab):
+def test_flash_bwd_dkdv_slab_mode():
     # dK/dV of the work items of one key block summed through per-item slabs (plain stores +
-    # convert pass) instead of f32 atomics: same numerics, every shape class
+    # convert pass): every shape class
+    _bwd_check(1, 4096, 4096, 4, 1, 128, True)
+    _bwd_check(1, 2048, 2048, 8, 2, 64, True)
+    _bwd_check(2, 100, 300, 4, 2, 64, True)
+    _bwd_check(1, 300, 100, 2, 2, 128, False)
+    _bwd_check(2, 1024, 1024, 8, 2, 128, False)
+
+
+@pytest.mark.parametrize("D", [64, 128])
+def test_flash_bwd_dkdv_bitwise_repeatable(D):
+    # four key blocks, up to 16 work items per block (chunk 8), GQA reduction in registers: the
+    # slabs are plain stores summed in item order, so two calls give the same dK / dV bits (dQ is
+    # accumulated with f32 atomics and is not asserted)
+    B, S, Hq, Hkv = 1, 1024, 4, 1
+    q, k, v = _attn_inputs(B, S, S, Hq, Hkv, D)
+    o, lse = ops.flash_attn_fwd_lse(q, k, v, causal=True)
+    do = torch.randn_like(o)
     ext = ops.ext()
-    ext.flash_attn_set_knob(5, slab)
+    ext.flash_attn_set_knob(1, 8)
     try:
-        _bwd_check(1, 4096, 4096, 4, 1, 128, True)
-        _bwd_check(1, 2048, 2048, 8, 2, 64, True)
-        _bwd_check(2, 100, 300, 4, 2, 64, True)
-        _bwd_check(1, 300, 100, 2, 2, 128, False)
-        _bwd_check(2, 1024, 1024, 8, 2, 128, False)
+        grads = []
+        for _ in range(2):
+            dq, dk, dv = (torch.empty_like(t) for t in (q, k, v))
+            ext.flash_attn_bwd(q, k, v, o, do, lse, dq, dk, dv, 1.0 / math.sqrt(D), True, 0)
+            grads.append((dk, dv))
     finally:
-        ext.flash_attn_set_knob(5, -1)
+        ext.flash_attn_set_knob(1, -1)
+    assert torch.equal(grads[0][0], grads[1][0])
+    assert torch.equal(grads[0][1], grads[1][1])
+    assert grads[0][0].float().abs().max().item() > 0 and grads[0][1].float().abs().max().item() > 0
+
+
+@pytest.mark.parametrize("D", [64, 128])
+def test_flash_bwd_odd_row_count(D):
+    # B * Hq * Sq = 33 is odd (the row constants in front of the slabs in the workspace), and a
+    # single partial query tile / key block is the smallest sequence the kernel accepts
+    _bwd_check(1, 33, 33, 1, 1, D, True)
+
+
+def test_flash_bwd_unknown_knob_raises():
+    with pytest.raises(RuntimeError):
+        ops.ext().flash_attn_set_knob(5, 0)
 
 
 def test_flash_bwd_cross_lengths():
