@@ -33,7 +33,7 @@ def main():
                     help="TP rehearsal on a one-GPU box: every rank on cuda:0, gloo process group (the decode "
                          "all-reduces and vocabulary gather run on the one-shot peer kernels over IPC, so decode is "
                          "still captured in hipGraphs); prefill eager")
-    ap.add_argument("--quantized", default=None, choices=[None, "per_tensor_symmetric", "per_channel_symmetric"])
+    ap.add_argument("--quantized", default=None, choices=[None, "per_tensor_symmetric", "per_channel_symmetric", "mxfp4"])
     ap.add_argument("--report", default="gpurun_out/benchmark_report.json")
     ap.add_argument("--weight-layout", action="store_true",
                     help="measured weight-layout pass at the prompt size (trace/weight_layout.py)")

@@ -4,6 +4,8 @@
         --quantization_type per_channel_symmetric --prompt_ids 1,2,3
 The decoder and lm_head linears hold int8 weights with fp32 scales; decode reads them directly in
 the skinny-GEMM kernel (csrc/gemv.hip), prefill dequantises into the GEMM.
+`--quantization_type mxfp4` stores them as MXFP4 instead (4-bit e2m1 codes with one E8M0 scale per
+32 in-features, 4.25 bits per weight; csrc/gemv_mx.hip).
 """
 
 import argparse
@@ -23,7 +25,7 @@ def main(argv=None):
     p.add_argument("--max_prompt_length", type=int, default=128)
     p.add_argument("--sequence_length", type=int, default=256)
     p.add_argument("--quantization_type", default="per_channel_symmetric",
-                   choices=["per_tensor_symmetric", "per_channel_symmetric"])
+                   choices=["per_tensor_symmetric", "per_channel_symmetric", "mxfp4"])
     p.add_argument("--prompt_ids", action="append", default=None, help="comma-separated token ids")
     a = p.parse_args(argv)
     r = LlamaRunner(model_path=a.model_path, tokenizer_path=a.model_path)

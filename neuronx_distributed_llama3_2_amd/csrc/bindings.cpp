@@ -59,6 +59,10 @@ int topk_sample_launch(const void*, int, int64_t, int, int, int, float, const fl
 int gemv_launch(const void*, int64_t, const void*, int64_t, int, const float*, float, const void*, void*, int64_t, int, int,
                 int, int, hipStream_t);
 int dequant_int8_launch(const void*, int64_t, const float*, float, void*, int, int, hipStream_t);
+int mx_gemv_launch(const void*, int64_t, const void*, int64_t, const void*, int64_t, const void*, void*, int64_t, int, int,
+                   int, int, hipStream_t);
+int mx_gemv_rows_per_wave(int, int);
+int mx_dequant_launch(const void*, int64_t, const void*, int64_t, void*, int, int, hipStream_t);
 int expert_gemv_launch(const void*, int64_t, const void*, int64_t, int64_t, const int32_t*, int, int, void*, int64_t, int,
                        int, int, hipStream_t);
 void dgemv_set_knob(int, int);
@@ -765,6 +769,60 @@ void dequant_int8(at::Tensor w, c10::optional<at::Tensor> scale, double tscale, 
            "dequant_int8");
 }
 
+// MXFP4 operands (csrc/gemv_mx.hip): packed uint8 [Nw, K/2] + E8M0 scale uint8 [Nw, K/32], unit inner
+// strides, 16-byte aligned rows of packed codes
+static void check_mx(const at::Tensor& w, const at::Tensor& scale, int64_t K, const char* op) {
+  check_cuda(w, "w");
+  check_cuda(scale, "scale");
+  TORCH_CHECK(w.scalar_type() == at::kByte && scale.scalar_type() == at::kByte, op, ": packed weight and scale must be uint8");
+  TORCH_CHECK(w.dim() == 2 && scale.dim() == 2 && w.stride(1) == 1 && scale.stride(1) == 1, op,
+              ": 2-D weight / scale with unit inner strides");
+  TORCH_CHECK(K >= 32 && K % 32 == 0 && w.size(1) == K / 2 && scale.size(1) == K / 32 && scale.size(0) == w.size(0), op,
+              ": weight [Nw, K/2] and scale [Nw, K/32] with K a multiple of 32");
+  TORCH_CHECK(w.stride(0) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, op,
+              ": 16-byte aligned weight rows required");
+  TORCH_CHECK(w.device() == scale.device(), op, ": weight and scale on different devices");
+}
+
+// y[M, N] = x[M, K] @ deq(W)^T (W MXFP4 [Nw, K], Nw = N or 2N with glu), optional bias [Nw]; M <= 8.
+void mx_gemv(at::Tensor x, at::Tensor w, at::Tensor scale, c10::optional<at::Tensor> bias, at::Tensor y, bool glu) {
+  check_cuda(x, "x");
+  check_bf16(x, "x");
+  check_bf16(y, "y");
+  check_cuda(y, "y");
+  TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && x.stride(1) == 1 && y.stride(1) == 1, "mx_gemv: 2-D x / y, unit inner strides");
+  const int64_t M = x.size(0), K = x.size(1), N = y.size(1);
+  check_mx(w, scale, K, "mx_gemv");
+  TORCH_CHECK(M >= 1 && M <= 8 && y.size(0) == M, "mx_gemv: 1 <= M <= 8");
+  TORCH_CHECK(N >= 1 && w.size(0) == (glu ? 2 * N : N), "mx_gemv: weight shape mismatch");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "mx_gemv: 16-byte aligned activation rows required");
+  TORCH_CHECK(x.device() == w.device() && y.device() == w.device(), "mx_gemv: operands on different devices");
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    check_bf16(*bias, "bias");
+    check_cuda(*bias, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == w.size(0), "mx_gemv: bias must be [Nw]");
+    bp = bias->data_ptr();
+  }
+  check_rc(nxd::mx_gemv_launch(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), scale.data_ptr(), scale.stride(0), bp,
+                               y.data_ptr(), y.stride(0), (int)M, (int)N, (int)K, glu, cur_stream()),
+           "mx_gemv");
+}
+
+void mx_dequant(at::Tensor w, at::Tensor scale, at::Tensor out) {
+  check_bf16(out, "out");
+  check_cuda(out, "out");
+  TORCH_CHECK(out.dim() == 2 && out.is_contiguous(), "mx_dequant: out must be contiguous [N, K]");
+  const int64_t N = out.size(0), K = out.size(1);
+  check_mx(w, scale, K, "mx_dequant");
+  TORCH_CHECK(N >= 1 && w.size(0) == N && out.device() == w.device(), "mx_dequant: out [N, K] vs weight [N, K/2]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0, "mx_dequant: 16-byte aligned out required");
+  check_rc(nxd::mx_dequant_launch(w.data_ptr(), w.stride(0), scale.data_ptr(), scale.stride(0), out.data_ptr(), (int)N,
+                                  (int)K, cur_stream()),
+           "mx_dequant");
+}
+
 // main_grad [M, N] fp32 += dy [T, M]^T x [T, N] (csrc/wgrad_gemm.hip): token-major bf16 operands with
 // unit inner strides, row strides multiples of 8 elements, T % 32 == 0; splits <= 0 -> auto.
 void wgrad_gemm(at::Tensor mg, at::Tensor dy, at::Tensor x, int64_t splits) {
@@ -1096,6 +1154,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("gemv", &gemv);
   m.def("dequant_int8", &dequant_int8);
   m.def("expert_gemv", &expert_gemv);
+  m.def("mx_gemv", &mx_gemv);
+  m.def("mx_dequant", &mx_dequant);
+  m.def("mx_gemv_rows_per_wave", [](int64_t N, int64_t K) { return nxd::mx_gemv_rows_per_wave((int)N, (int)K); });
   m.def("grouped_gemm", &grouped_gemm);
   m.def("wgrad_gemm", &wgrad_gemm);
   m.def("dense_gemm", &dense_gemm, py::arg("layout"), py::arg("epi"), py::arg("a"), py::arg("b"), py::arg("c"),

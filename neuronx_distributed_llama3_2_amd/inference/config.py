@@ -44,6 +44,7 @@ class InferenceConfig:
         self.bucket_n_active_tokens = False
         self.quantized = kwargs.pop("quantized", False)
         self.quantized_checkpoints_path = kwargs.pop("quantized_checkpoints_path", None)
+        # "per_tensor_symmetric" / "per_channel_symmetric" (int8) or "mxfp4" (block-scaled 4-bit)
         self.quantization_type = kwargs.pop("quantization_type", "per_tensor_symmetric")
         self.trace_tokengen_model = kwargs.pop("trace_tokengen_model", True)
         self.speculation_length = kwargs.pop("speculation_length", 0)

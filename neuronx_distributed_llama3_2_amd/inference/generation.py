@@ -201,10 +201,14 @@ class LlamaForCausalLMInference:
     def _quantize(self) -> None:
         """Swap the decoder / lm_head linears for int8 weight-only layers (reference flow:
         run_llama_quantized.py -> quantize_pytorch_model_per_*_symmetric + convert)."""
-        from ..quantization import convert, get_default_custom_qconfig_dict, get_default_per_channel_custom_qconfig_dict
+        from ..quantization import (convert, get_default_custom_qconfig_dict, get_default_mxfp4_qconfig_dict,
+                                    get_default_per_channel_custom_qconfig_dict)
 
         qt = str(self.config.quantization_type)
-        q = get_default_per_channel_custom_qconfig_dict() if "channel" in qt else get_default_custom_qconfig_dict()
+        if qt == "mxfp4":   # MXFP4 weight-only layers (quantization_layers.MXFP4*Parallel)
+            q = get_default_mxfp4_qconfig_dict()
+        else:
+            q = get_default_per_channel_custom_qconfig_dict() if "channel" in qt else get_default_custom_qconfig_dict()
         convert(self.model, q, inplace=True)
 
     # ------------------------------------------------------------------ construction

@@ -35,7 +35,7 @@ import torch.distributed as dist
 
 from .. import ops
 from ..ops.gemm import linear as _linear
-from ..ops.gemv import skinny_linear
+from ..ops.gemv import mx_linear, skinny_linear
 from ..parallel_layers import parallel_state as ps
 from ..parallel_layers.parallel_state import get_tensor_model_parallel_size
 
@@ -469,6 +469,8 @@ class DecoderInferenceMixin:
             w, b = mod.weight, getattr(mod, "bias", None)
         if not use_bias:
             b = None
+        if w.dtype == torch.uint8:   # MXFP4: packed codes + E8M0 block scales (ops/gemv.py)
+            return mx_linear(x, w, mod.scale, b, glu=glu)
         scale = mod._row_scale() if w.dtype == torch.int8 else None
         M = x.numel() // x.shape[-1]
         if w.dtype == torch.int8 or (M <= 8 and x.is_cuda):

@@ -42,7 +42,7 @@ class _MoEInferenceBase(LlamaForCausalLMInference):
         return moe_config_from_dir(path)
 
     def _quantize(self) -> None:
-        raise NotImplementedError("int8 weight-only quantization is implemented for dense decoders only")
+        raise NotImplementedError("weight-only quantization (int8, MXFP4) is implemented for dense decoders only")
 
 
 class MixtralForCausalLMInference(_MoEInferenceBase):

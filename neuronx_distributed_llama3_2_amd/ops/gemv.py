@@ -1,6 +1,24 @@
 """Decode-path linear ops (csrc/gemv.hip): skinny GEMM for M <= 8 tokens with bf16 or int8 weights,
 optional per-row / per-tensor scale, bias and fused SwiGLU epilogue; int8 -> bf16 dequantisation
-for the prefill path.  CPU / large-M calls fall back to dequantise + GEMM."""
+for the prefill path.  CPU / large-M calls fall back to dequantise + GEMM.
+
+MXFP4 weight-only format (csrc/gemv_mx.hip; OCP Microscaling Formats v1.0).  This docstring is the
+definition every other layer refers to:
+
+* Block: 32 consecutive elements along the in-features axis of an [out, in] weight
+  (in % 32 != 0 raises ValueError).
+* Scale: one E8M0 byte e per block, value 2^(e-127), stored as uint8 [out, in/32].
+* Element: e2m1 as a 4-bit code s<<3 | i; the magnitude i indexes {0, 0.5, 1, 1.5, 2, 3, 4, 6}.
+* Packing: byte j of a row holds element 2j in its low nibble and element 2j+1 in its high nibble,
+  stored as uint8 [out, in/2].  Plain uint8 storage, no float4 / e8m0 torch dtypes.
+
+That is 4.25 bits per weight.  The quantizer: per block amax = max|v|, X = floor(log2(amax)) - 2
+(from frexp, never a float log2), e = X + 127 clamped to [1, 254]; elements are v / 2^X rounded to
+the nearest grid value, ties to the code with an even mantissa bit, saturating at +-6.  An all-zero
+block gets e = 127 and zero codes; non-finite input raises ValueError.  The quantizer emits neither
+e = 0 nor e = 255; the dequantizer below reads e = 0 as 2^-127 and e = 255 as NaN (what the GPU
+kernels do with those two bytes is unspecified).  Every e2m1 value has at most two significant bits,
+so code * 2^X is exact in bf16 over the normal range: dequantisation to bf16 loses nothing."""
 
 from __future__ import annotations
 
@@ -83,6 +101,104 @@ def expert_linear(x: torch.Tensor, w_t: torch.Tensor, eidx: torch.Tensor, xdiv: 
         return y
     rows = x.reshape(-1, K).index_select(0, torch.arange(P, device=x.device) // xdiv)
     y = torch.bmm(rows.unsqueeze(1), w_t.index_select(0, eidx.reshape(-1).long()).transpose(1, 2)).squeeze(1)
+    if glu:
+        from .activations import swiglu
+
+        y = swiglu(y)
+    return y
+
+
+MX_BLOCK = 32
+_E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    """float [out, in] -> (packed uint8 [out, in/2], E8M0 scale uint8 [out, in/32]); the format and
+    the rounding rule are in the module docstring.  Pure torch, on w's device."""
+    if not w.is_floating_point():
+        raise TypeError(f"quantize_mxfp4 needs a floating-point weight, got {w.dtype}")
+    if w.dim() < 1 or w.shape[-1] % MX_BLOCK != 0 or w.shape[-1] == 0:
+        raise ValueError(f"MXFP4 blocks are {MX_BLOCK} elements along the last axis; got shape {tuple(w.shape)}")
+    v = w.detach().float()
+    if not bool(torch.isfinite(v).all()):
+        raise ValueError("quantize_mxfp4: non-finite weight")
+    lead, K = tuple(v.shape[:-1]), v.shape[-1]
+    b = v.reshape(lead + (K // MX_BLOCK, MX_BLOCK))
+    amax = b.abs().amax(dim=-1)
+    _, ex = torch.frexp(amax)                       # amax = m * 2^ex, 0.5 <= m < 1: floor(log2) = ex - 1
+    e = (ex.to(torch.int32) - 3 + 127).clamp(1, 254)
+    e = torch.where(amax == 0, torch.full_like(e, 127), e)
+    nx = (127 - e).unsqueeze(-1)                    # -X; 2^-X applied in two exact steps, each a normal f32
+    h = torch.div(nx, 2, rounding_mode="floor")
+    a = (b * torch.exp2(h.float())) * torch.exp2((nx - h).float())
+    mag = a.abs().clamp(max=6.0)
+    # nearest grid value, ties to the even code: the grid step is 0.5 below 2, 1 below 4, 2 above,
+    # and torch.round is round-half-to-even on the step count
+    code = torch.where(mag < 2.0, torch.round(mag * 2.0),
+                       torch.where(mag < 4.0, torch.round(mag) + 2.0, torch.round(mag * 0.5) + 4.0)).to(torch.uint8)
+    code = code | (torch.signbit(a).to(torch.uint8) << 3)
+    code = code.reshape(lead + (K // 2, 2))
+    packed = code[..., 0] | (code[..., 1] << 4)
+    return packed.contiguous(), e.to(torch.uint8).contiguous()
+
+
+def _dequantize_mxfp4_torch(packed: torch.Tensor, scale: torch.Tensor, dtype) -> torch.Tensor:
+    lut = torch.tensor(_E2M1_VALUES + tuple(-x for x in _E2M1_VALUES), dtype=torch.float32, device=packed.device)
+    codes = torch.stack((packed & 0xF, packed >> 4), dim=-1).reshape(packed.shape[:-1] + (packed.shape[-1] * 2,))
+    vals = lut[codes.long()]
+    e = scale.to(torch.float32)
+    s = torch.where(e == 255, torch.full_like(e, float("nan")), torch.exp2(e - 127.0))
+    return (vals.reshape(scale.shape + (MX_BLOCK,)) * s.unsqueeze(-1)).reshape(vals.shape).to(dtype)
+
+
+def _check_mxfp4(packed: torch.Tensor, scale: torch.Tensor) -> None:
+    if packed.dtype != torch.uint8 or scale.dtype != torch.uint8:
+        raise TypeError("MXFP4 weights are uint8 packed codes + uint8 E8M0 scales")
+    if packed.shape[-1] % (MX_BLOCK // 2) != 0 or packed.shape[:-1] != scale.shape[:-1] or \
+            scale.shape[-1] * (MX_BLOCK // 2) != packed.shape[-1]:
+        raise ValueError(f"MXFP4 shapes: packed [out, in/2] and scale [out, in/32], got {tuple(packed.shape)} "
+                         f"and {tuple(scale.shape)}")
+
+
+def _mx_native_ok(packed: torch.Tensor, scale: torch.Tensor) -> bool:
+    return packed.dim() == 2 and packed.stride(1) == 1 and scale.stride(1) == 1 and packed.stride(0) % 16 == 0 and \
+        packed.data_ptr() % 16 == 0 and packed.numel() > 0
+
+
+def dequantize_mxfp4(packed: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """MXFP4 (packed [out, in/2], scale [out, in/32]) -> dtype [out, in].  On the GPU the bf16 result
+    comes from the mx_dequant kernel (bit-identical to the torch form here)."""
+    _check_mxfp4(packed, scale)
+    if use_native(packed, scale) and dtype == torch.bfloat16 and _mx_native_ok(packed, scale):
+        out = torch.empty((packed.shape[0], packed.shape[1] * 2), dtype=torch.bfloat16, device=packed.device)
+        ext().mx_dequant(packed, scale, out)
+        return out
+    return _dequantize_mxfp4_torch(packed, scale, dtype)
+
+
+def mx_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
+              glu: bool = False) -> torch.Tensor:
+    """x [..., K] @ deq(W)^T (+ bias) for MXFP4 W (packed [Nw, K/2], scale [Nw, K/32]); glu=True:
+    W = [gate; up] rows and the result is silu(gate) * up of width Nw / 2.  Decode-sized bf16 inputs
+    on the GPU (M <= 8) read the 4-bit weights directly (mx_gemv); everything else dequantises and
+    goes through the GEMM."""
+    _check_mxfp4(packed, scale)
+    K = x.shape[-1]
+    if packed.dim() != 2 or packed.shape[1] * 2 != K:
+        raise ValueError(f"mx_linear: x [..., {K}] against packed weight {tuple(packed.shape)}")
+    lead = x.shape[:-1]
+    M = x.numel() // K
+    Nw = packed.shape[0]
+    N = Nw // 2 if glu else Nw
+    if use_native(x, packed, scale) and 1 <= M <= 8 and x.dtype == torch.bfloat16 and N >= 1 and \
+            _mx_native_ok(packed, scale) and (bias is None or bias.dtype == torch.bfloat16):
+        x2 = x.reshape(M, K)
+        if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
+            x2 = x2.contiguous()
+        y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+        ext().mx_gemv(x2, packed, scale, bias.contiguous() if bias is not None else None, y, glu)
+        return y.view(lead + (N,))
+    y = _linear(x, dequantize_mxfp4(packed, scale, x.dtype), bias)
     if glu:
         from .activations import swiglu
 

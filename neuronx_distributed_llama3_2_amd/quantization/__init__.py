@@ -1,15 +1,19 @@
-"""int8 weight-only quantization (reference: src/neuronx_distributed/quantization/)."""
+"""int8 and MXFP4 weight-only quantization (reference: src/neuronx_distributed/quantization/)."""
 
+from ..ops.gemv import dequantize_mxfp4, mx_linear, quantize_mxfp4  # noqa: F401
 from .dequantize import direct_cast_dequantize, scale_dequantize  # noqa: F401
 from .observer import PerChannelAbsMaxObserver  # noqa: F401
 from .quantization_config import (  # noqa: F401
     QuantizationType,
     QuantizedDtype,
     get_default_custom_qconfig_dict,
+    get_default_mxfp4_qconfig_dict,
     get_default_per_channel_custom_qconfig_dict,
 )
 from .quantization_layers import (  # noqa: F401
     BaseQuantizeParallelLinear,
+    MXFP4ColumnParallel,
+    MXFP4RowParallel,
     QuantizedColumnParallel,
     QuantizedExpertFusedColumnParallel,
     QuantizedExpertFusedRowParallel,

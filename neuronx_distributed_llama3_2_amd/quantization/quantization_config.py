@@ -19,10 +19,12 @@ class _ContainsEnumMeta(enum.EnumMeta):
 class QuantizationType(Enum, metaclass=_ContainsEnumMeta):
     PER_TENSOR_SYMMETRIC = "per_tensor_symmetric"
     PER_CHANNEL_SYMMETRIC = "per_channel_symmetric"
+    MX_BLOCK = "mxfp4"   # OCP microscaling: one E8M0 scale per 32 in-features (format: ops/gemv.py)
 
 
 class QuantizedDtype(Enum, metaclass=_ContainsEnumMeta):
     INT8 = torch.int8
+    MXFP4 = "mxfp4"      # 4-bit e2m1 codes packed two per uint8
 
 
 class BASE_QCONFIG_DICT_TYPE(TypedDict):
@@ -51,3 +53,14 @@ def get_default_custom_qconfig_dict() -> BASE_QCONFIG_DICT_TYPE:
 
 def get_default_per_channel_custom_qconfig_dict() -> PER_CHANNEL_QCONFIG_DICT_TYPE:
     return dict(_DEFAULT_PER_CHANNEL_QCONFIG_DICT)
+
+
+def get_default_mxfp4_qconfig_dict() -> BASE_QCONFIG_DICT_TYPE:
+    return {"quantization_type": QuantizationType.MX_BLOCK, "quantized_dtype": QuantizedDtype.MXFP4}
+
+
+def is_mxfp4_qconfig(q_config) -> bool:
+    if not q_config:
+        return False
+    qd = q_config.get("quantized_dtype")
+    return qd == QuantizedDtype.MXFP4 or qd == QuantizedDtype.MXFP4.value

@@ -7,6 +7,9 @@ channel [out, 1] — sharded with the weight when the channel axis is the partit
   directly and applies the scale in the epilogue — half the HBM bytes of bf16 decode;
 * prefill / training-size inputs: one int8 -> bf16 dequantisation kernel, then the tuned GEMM.
 Same collectives as the float layers (TP all-reduce / SP reduce-scatter / gather_output).
+
+MXFP4ColumnParallel / MXFP4RowParallel are the same pair with MXFP4 storage (packed 4-bit e2m1 codes and
+one E8M0 scale per 32 in-features, both uint8; format in ops/gemv.py, kernels in csrc/gemv_mx.hip).
 """
 
 from __future__ import annotations
@@ -18,7 +21,7 @@ from torch import nn
 from torch.nn.parameter import Parameter
 
 from ..modules.moe.moe_parallel_layers import ExpertFusedColumnParallelLinear, ExpertFusedRowParallelLinear
-from ..ops.gemv import dequantize_weight, skinny_linear
+from ..ops.gemv import MX_BLOCK, dequantize_weight, mx_linear, quantize_mxfp4, skinny_linear
 from ..parallel_layers import mappings
 from ..parallel_layers import parallel_state as ps
 from ..parallel_layers import sp
@@ -254,6 +257,125 @@ class QuantizedExpertFusedRowParallel(QuantizedExpertFusedColumnParallel):
         if self.reduce_output and ps.get_tensor_model_parallel_size() > 1:
             out = mappings.reduce_from_tensor_model_parallel_region(out)
         return out
+
+
+class _MXFP4ParallelLinear(nn.Module):
+    """MXFP4 weight-only storage of a tensor-parallel linear (format: ops/gemv.py): `weight` is the
+    packed uint8 [out, in/2] parameter, `scale` the E8M0 uint8 [out, in/32] one; both are sharded
+    along the layer's partition dim (blocks run along `in`, so a row-parallel shard needs its local
+    `in` to be a multiple of 32).  Decode-sized inputs read the 4-bit weights directly (mx_gemv);
+    larger ones dequantise to bf16 and take the tuned GEMM."""
+
+    def _setup_mx(self, out_features: int, in_features: int, partition_dim: int, stride: int, device) -> None:
+        if in_features % MX_BLOCK != 0:
+            raise ValueError(f"MXFP4 needs the local in-features ({in_features}) to be a multiple of {MX_BLOCK}")
+        self.quantization_type = QuantizationType.MX_BLOCK
+        self.quantized_dtype = QuantizedDtype.MXFP4.value
+        self.weight = Parameter(torch.zeros((out_features, in_features // 2), dtype=torch.uint8, device=device),
+                                requires_grad=False)
+        # e = 127 (scale 1) with zero codes: an unloaded layer dequantises to zeros
+        self.scale = Parameter(torch.full((out_features, in_features // MX_BLOCK), 127, dtype=torch.uint8, device=device),
+                               requires_grad=False)
+        set_tensor_model_parallel_attributes(self.weight, True, partition_dim, stride)
+        set_tensor_model_parallel_attributes(self.scale, True, partition_dim, stride)
+
+    def quantize_from(self, w_float: torch.Tensor) -> None:
+        """Quantise a float weight of this layer's (local) [out, in] shape into weight + scale."""
+        q, s = quantize_mxfp4(w_float)
+        with torch.no_grad():
+            self.weight.copy_(q.to(self.weight.device))
+            self.scale.copy_(s.to(self.scale.device))
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                              error_msgs):
+        wk = prefix + "weight"
+        if wk in state_dict and state_dict[wk].is_floating_point():
+            state_dict[wk], state_dict[prefix + "scale"] = quantize_mxfp4(state_dict[wk])
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                      error_msgs)
+
+    def _matmul(self, x: torch.Tensor) -> torch.Tensor:
+        return mx_linear(x, self.weight, self.scale)
+
+    def _copy_bias(self, mod) -> None:
+        if mod.bias is not None:
+            with torch.no_grad():
+                self.bias.copy_(mod.bias)
+
+
+class MXFP4ColumnParallel(_MXFP4ParallelLinear):
+    def __init__(self, input_size: int, output_size: int, bias: bool = True, gather_output: bool = True,
+                 dtype: torch.dtype = torch.bfloat16, device: Optional[torch.device] = None, stride: int = 1,
+                 sequence_parallel_enabled: bool = False, keep_master_weight: bool = False,
+                 quantization_type: Any = None, quantized_dtype: Any = QuantizedDtype.MXFP4,
+                 quantization_per_channel_axis: Optional[int] = None, q_config: Optional[dict] = None, **kw):
+        super().__init__()
+        tp = ps.get_tensor_model_parallel_size()
+        self.input_size, self.output_size = input_size, output_size
+        self.output_size_per_partition = divide(output_size, tp)
+        self.gather_output, self.stride, self.dtype = gather_output, stride, dtype
+        self.sequence_parallel_enabled = sequence_parallel_enabled and tp > 1
+        self._setup_mx(self.output_size_per_partition, input_size, 0, stride, device)
+        if bias:
+            self.bias = Parameter(torch.zeros(self.output_size if gather_output else self.output_size_per_partition,
+                                              dtype=dtype, device=device), requires_grad=False)
+            if not gather_output:
+                set_tensor_model_parallel_attributes(self.bias, True, 0, stride)
+        else:
+            self.register_parameter("bias", None)
+
+    forward = QuantizedColumnParallel.forward
+
+    @classmethod
+    def from_float(cls, mod: ColumnParallelLinear, q_config: BASE_QCONFIG_DICT_TYPE = None):
+        new = cls(mod.input_size, mod.output_size, bias=mod.bias is not None, gather_output=mod.gather_output,
+                  dtype=mod.weight.dtype if mod.weight.is_floating_point() else torch.bfloat16,
+                  device=mod.weight.device, stride=mod.stride,
+                  sequence_parallel_enabled=mod.sequence_parallel_enabled, q_config=q_config)
+        if mod.weight.device.type != "meta":
+            new.quantize_from(mod.weight)
+            new._copy_bias(mod)
+        return new
+
+
+class MXFP4RowParallel(_MXFP4ParallelLinear):
+    def __init__(self, input_size: int, output_size: int, bias: bool = True, input_is_parallel: bool = False,
+                 dtype: torch.dtype = torch.bfloat16, device: Optional[torch.device] = None, stride: int = 1,
+                 sequence_parallel_enabled: bool = False, keep_master_weight: bool = False,
+                 quantization_type: Any = None, quantized_dtype: Any = QuantizedDtype.MXFP4,
+                 quantization_per_channel_axis: Optional[int] = None, q_config: Optional[dict] = None, **kw):
+        super().__init__()
+        tp = ps.get_tensor_model_parallel_size()
+        self.input_size, self.output_size = input_size, output_size
+        self.input_size_per_partition = divide(input_size, tp)
+        self.input_is_parallel, self.stride, self.dtype = input_is_parallel, stride, dtype
+        self.sequence_parallel_enabled = sequence_parallel_enabled and tp > 1
+        self._setup_mx(output_size, self.input_size_per_partition, 1, stride, device)
+        if bias:
+            self.bias = Parameter(torch.zeros(output_size, dtype=dtype, device=device), requires_grad=False)
+        else:
+            self.register_parameter("bias", None)
+
+    forward = QuantizedRowParallel.forward
+
+    @classmethod
+    def from_float(cls, mod: RowParallelLinear, q_config: BASE_QCONFIG_DICT_TYPE = None):
+        new = cls(mod.input_size, mod.output_size, bias=mod.bias is not None, input_is_parallel=mod.input_is_parallel,
+                  dtype=mod.weight.dtype if mod.weight.is_floating_point() else torch.bfloat16,
+                  device=mod.weight.device, stride=mod.stride,
+                  sequence_parallel_enabled=mod.sequence_parallel_enabled, q_config=q_config)
+        if mod.weight.device.type != "meta":
+            new.quantize_from(mod.weight)
+            new._copy_bias(mod)
+        return new
+
+
+class MXFP4ExpertFusedUnsupported:
+    """The expert-fused MoE linears have no MXFP4 form."""
+
+    @classmethod
+    def from_float(cls, mod, q_config=None):
+        raise NotImplementedError("MXFP4 weight-only quantization covers the dense linears only, not MoE experts")
 
 
 def _qc(quantization_type, quantized_dtype, axis):

@@ -14,5 +14,17 @@ DEFAULT_QUANT_MODULE_MAPPINGS: Dict[Callable, Any] = {
 }
 
 
+MXFP4_QUANT_MODULE_MAPPINGS: Dict[Callable, Any] = {
+    parallel_layers.ColumnParallelLinear: q_layers.MXFP4ColumnParallel,
+    parallel_layers.RowParallelLinear: q_layers.MXFP4RowParallel,
+    moe_parallel_layers.ExpertFusedColumnParallelLinear: q_layers.MXFP4ExpertFusedUnsupported,
+    moe_parallel_layers.ExpertFusedRowParallelLinear: q_layers.MXFP4ExpertFusedUnsupported,
+}
+
+
 def get_default_quant_module_mappings() -> Dict[Callable, Any]:
     return DEFAULT_QUANT_MODULE_MAPPINGS
+
+
+def get_mxfp4_quant_module_mappings() -> Dict[Callable, Any]:
+    return MXFP4_QUANT_MODULE_MAPPINGS
