@@ -34,6 +34,7 @@ def main():
                          "all-reduces and vocabulary gather run on the one-shot peer kernels over IPC, so decode is "
                          "still captured in hipGraphs); prefill eager")
     ap.add_argument("--quantized", default=None, choices=[None, "per_tensor_symmetric", "per_channel_symmetric", "mxfp4"])
+    ap.add_argument("--kv-cache-dtype", default=None, choices=[None, "bfloat16", "mxfp8"])
     ap.add_argument("--report", default="gpurun_out/benchmark_report.json")
     ap.add_argument("--weight-layout", action="store_true",
                     help="measured weight-layout pass at the prompt size (trace/weight_layout.py)")
@@ -56,7 +57,8 @@ def main():
     icfg = InferenceConfig(tp_degree=world, batch_size=args.batch, seq_len=seq_len, max_context_length=args.prompt,
                            decode_graph_steps=args.graph_steps, use_hip_graphs=not args.no_graphs,
                            quantized=args.quantized is not None,
-                           quantization_type=args.quantized or "per_tensor_symmetric")
+                           quantization_type=args.quantized or "per_tensor_symmetric",
+                           kv_cache_dtype=args.kv_cache_dtype)
     torch.manual_seed(0)
     model = LlamaForCausalLMInference(mcfg, icfg, dtype=torch.bfloat16)
     layouts = None
@@ -86,7 +88,7 @@ def main():
                                   "tokens_per_s_per_seq": 1000.0 * max(1, args.new - 1) / max(1e-6, e2e_ms - cte_ms)}
     report["config"] = {"model": args.model, "tp": world, "gloo_gpu_rehearsal": bool(args.gloo_gpu), "batch": args.batch, "prompt": args.prompt,
                         "new_tokens": args.new, "dtype": "bf16", "graph_steps": args.graph_steps,
-                        "hip_graphs": not args.no_graphs, "quantized": args.quantized,
+                        "hip_graphs": not args.no_graphs, "quantized": args.quantized, "kv_cache_dtype": args.kv_cache_dtype,
                         "weight_layouts": None if layouts is None else {v: sum(1 for x in layouts.values() if x == v)
                                                                         for v in set(layouts.values())},
                         "data": "synthetic prompt, random-init weights"}

@@ -48,9 +48,13 @@ int embedding_fwd_launch(const int64_t*, const void*, void*, int64_t, int, int64
 int embedding_bwd_launch(const int64_t*, const void*, float*, int64_t, int, int64_t, int64_t, hipStream_t);
 int decode_attn_launch(const void*, const int64_t*, const void*, const void*, const int64_t*, const int*, const int*,
                        float*, float*, float*, int*, void*, const int64_t*, int, int, int, int, int, int, float, hipStream_t,
-                       int);
+                       int, const void*, const void*, const int64_t*);
 int kv_cache_write_launch(const void*, const void*, const int64_t*, void*, void*, const int64_t*, const int*, const int*,
                           int, int, int, int, int, hipStream_t);
+int kv_write_mx8_launch(const void*, const void*, const int64_t*, void*, void*, void*, void*, const int*, const int*, int, int,
+                        int, int, int, int, hipStream_t);
+int mx8_dequant_launch(const void*, const int64_t*, const void*, const int64_t*, void*, int64_t, int64_t, int64_t, int,
+                       hipStream_t);
 int argmax_launch(const void*, int, int64_t, int, int, int64_t*, hipStream_t);
 int greedy_advance_launch(const void*, int, int64_t, int, int, unsigned long long*, int64_t*, int64_t, int, int64_t*, int64_t*,
                           int64_t*, int*, hipStream_t);
@@ -564,11 +568,96 @@ bool decode_attn_oproj(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional
   return true;
 }
 
+// MXFP8 cache operands (csrc/kv_cache_mx.hip, format in ops/decode.py): codes uint8 [Bc, Hkv, Lmax, D]
+// and E8M0 scales uint8 [Bc, Hkv, Lmax, D / 32], unit inner strides, D % 32 == 0
+static void check_mx8(const at::Tensor& codes, const at::Tensor& scale, const char* n) {
+  check_cuda(codes, n);
+  check_cuda(scale, n);
+  TORCH_CHECK(codes.scalar_type() == at::kByte && scale.scalar_type() == at::kByte, n, ": codes and scales must be uint8");
+  TORCH_CHECK(codes.dim() == 4 && scale.dim() == 4, n, ": codes [B, Hkv, Lmax, D] and scales [B, Hkv, Lmax, D / 32]");
+  const int64_t D = codes.size(3);
+  TORCH_CHECK(D >= 32 && D % 32 == 0, n, ": head dim must be a multiple of 32");
+  TORCH_CHECK(scale.size(0) == codes.size(0) && scale.size(1) == codes.size(1) && scale.size(2) == codes.size(2) &&
+                  scale.size(3) == D / 32,
+              n, ": scale shape must be the code shape with D / 32 columns");
+  TORCH_CHECK(codes.stride(3) == 1 && (scale.stride(3) == 1 || scale.size(3) == 1), n, ": unit inner strides required");
+  TORCH_CHECK(codes.device() == scale.device(), n, ": codes and scales on different devices");
+}
+
+// codes * 2^(scale - 127) -> contiguous bf16 of the codes' shape (any outer strides, any alignment)
+at::Tensor mx8_dequant(at::Tensor codes, at::Tensor scale) {
+  check_mx8(codes, scale, "mx8_dequant");
+  at::Tensor out = at::empty(codes.sizes(), codes.options().dtype(at::kBFloat16));
+  const int64_t cs[3] = {codes.stride(0), codes.stride(1), codes.stride(2)};
+  const int64_t ss[3] = {scale.stride(0), scale.stride(1), scale.stride(2)};
+  check_rc(nxd::mx8_dequant_launch(codes.data_ptr(), cs, scale.data_ptr(), ss, out.data_ptr(), codes.size(0), codes.size(1),
+                                   codes.size(2), (int)codes.size(3), cur_stream()),
+           "mx8_dequant");
+  return out;
+}
+
 void decode_attn(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional<at::Tensor> cache_idx, at::Tensor seq_len,
-                 at::Tensor out, double scale, int64_t nsplit, int64_t window) {
+                 at::Tensor out, double scale, int64_t nsplit, int64_t window, c10::optional<at::Tensor> k_scale,
+                 c10::optional<at::Tensor> v_scale) {
   int64_t qs[3], os[3];
   bshd_strides(q, "q", qs);
   bshd_strides(out, "out", os);
+  // MXFP8 cache: the KV8 form of the MFMA kernel when it covers the call (M <= 16, D 64 / 128, contiguous
+  // 16-byte aligned caches); otherwise both caches are dequantized into scratch bf16 caches and
+  // the bf16 kernels below run on those -- static shapes, capturable, slower
+  TORCH_CHECK(k_scale.has_value() == v_scale.has_value(), "decode_attn: k_scale and v_scale go together");
+  const void *ksp = nullptr, *vsp = nullptr;
+  int64_t ss[3] = {0, 0, 0};
+  if (k_scale.has_value()) {
+    check_mx8(kc, *k_scale, "k_cache");
+    check_mx8(vc, *v_scale, "v_cache");
+    TORCH_CHECK(vc.sizes() == kc.sizes() && kc.device() == q.device() && vc.device() == q.device(), "cache shape / device mismatch");
+    const int64_t D8 = kc.size(3), Hkv8 = kc.size(1);
+    const bool covered = Hkv8 > 0 && q.size(2) % Hkv8 == 0 && (q.size(2) / Hkv8) * q.size(1) <= 16 && (D8 == 64 || D8 == 128) &&
+                         kc.is_contiguous() && vc.is_contiguous() && k_scale->is_contiguous() && v_scale->is_contiguous();
+    if (!covered) {
+      kc = mx8_dequant(kc, *k_scale);
+      vc = mx8_dequant(vc, *v_scale);
+    } else {
+      ksp = k_scale->data_ptr();
+      vsp = v_scale->data_ptr();
+      for (int i = 0; i < 3; ++i) ss[i] = k_scale->stride(i);
+    }
+  }
+  if (ksp != nullptr) {
+    const int B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
+    const int Hkv = kc.size(1), Lmax = kc.size(2);
+    TORCH_CHECK(kc.size(3) == D, "head dim mismatch");
+    TORCH_CHECK(nsplit >= 1 && nsplit * 128 >= Lmax, "nsplit * 128 must cover the cache length");
+    TORCH_CHECK(window >= 0, "window must be >= 0 (0: none)");
+    TORCH_CHECK(seq_len.scalar_type() == at::kInt && seq_len.numel() == B && seq_len.is_contiguous(), "seq_len must be int32 [B]");
+    const int* ci = nullptr;
+    if (cache_idx.has_value()) {
+      TORCH_CHECK(cache_idx->scalar_type() == at::kInt && cache_idx->numel() == B, "cache_idx must be int32 [B]");
+      ci = cache_idx->data_ptr<int>();
+    } else {
+      TORCH_CHECK(kc.size(0) >= B, "cache batch too small");
+    }
+    TORCH_CHECK(out.sizes() == q.sizes(), "out shape mismatch");
+    TORCH_CHECK(os[2] % 8 == 0 || Hq == 1, "out head stride must keep 16-byte alignment");
+    const int M = (Hq / Hkv) * T;
+    auto opts = q.options().dtype(at::kFloat);
+    at::Tensor po = at::empty({(int64_t)B * Hkv * nsplit * M * D}, opts);
+    at::Tensor pm = at::empty({(int64_t)B * Hkv * nsplit * M}, opts);
+    at::Tensor pl = at::empty({(int64_t)B * Hkv * nsplit * M}, opts);
+    const int64_t cs[3] = {kc.stride(0), kc.stride(1), kc.stride(2)};
+    const int rc = nxd::decode_attn_launch(q.data_ptr(), qs, kc.data_ptr(), vc.data_ptr(), cs, ci, seq_len.data_ptr<int>(),
+                                           po.data_ptr<float>(), pm.data_ptr<float>(), pl.data_ptr<float>(), nullptr,
+                                           out.data_ptr(), os, B, T, Hq, Hkv, D, (int)nsplit, (float)scale, cur_stream(),
+                                           window >= Lmax ? 0 : (int)window, ksp, vsp, ss);
+    if (rc != -4) {
+      check_rc(rc, "decode_attn (mxfp8)");
+      nxd::decode_attn_set_prefetch(nullptr, 0, nullptr, 0, 0);
+      return;
+    }
+    kc = mx8_dequant(kc, *k_scale);   // misaligned rows, or the MFMA kernel is switched off
+    vc = mx8_dequant(vc, *v_scale);
+  }
   check_bf16(kc, "k_cache");
   check_bf16(vc, "v_cache");
   TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.sizes() == kc.sizes() && vc.is_contiguous(),
@@ -601,18 +690,44 @@ void decode_attn(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional<at::T
   check_rc(nxd::decode_attn_launch(q.data_ptr(), qs, kc.data_ptr(), vc.data_ptr(), cs, ci, seq_len.data_ptr<int>(),
                                    po.data_ptr<float>(), pm.data_ptr<float>(), pl.data_ptr<float>(), counters, out.data_ptr(),
                                    os, B, T, Hq, Hkv, D, (int)nsplit, (float)scale, cur_stream(),
-                                   window >= Lmax ? 0 : (int)window),
+                                   window >= Lmax ? 0 : (int)window, nullptr, nullptr, nullptr),
            "decode_attn");
   nxd::decode_attn_set_prefetch(nullptr, 0, nullptr, 0, 0);   // armed ranges never outlive one call
 }
 
 // k, v: [B, T, Hkv, D] strided; caches [Bc, Hkv, Lmax, D]; pos: int32 [B] position of token 0
+// k_scale / v_scale: MXFP8 caches (uint8 codes + E8M0 scales, contiguous): the rows are quantized on the way in
 void kv_cache_write(at::Tensor k, at::Tensor v, at::Tensor kc, at::Tensor vc, c10::optional<at::Tensor> cache_idx,
-                    at::Tensor pos) {
+                    at::Tensor pos, c10::optional<at::Tensor> k_scale, c10::optional<at::Tensor> v_scale) {
   int64_t ks[3], vs[3];
   bshd_strides(k, "k", ks);
   bshd_strides(v, "v", vs);
   TORCH_CHECK(ks[0] == vs[0] && ks[1] == vs[1] && ks[2] == vs[2] && k.sizes() == v.sizes(), "k/v layouts must match");
+  TORCH_CHECK(k_scale.has_value() == v_scale.has_value(), "kv_cache_write: k_scale and v_scale go together");
+  if (k_scale.has_value()) {
+    check_mx8(kc, *k_scale, "k_cache");
+    check_mx8(vc, *v_scale, "v_cache");
+    TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous() && k_scale->is_contiguous() && v_scale->is_contiguous() &&
+                    vc.sizes() == kc.sizes(),
+                "kv_cache_write: MXFP8 caches and scales must be contiguous and of one shape");
+    check_aligned16(kc, "k_cache");
+    check_aligned16(vc, "v_cache");
+    const int B = k.size(0), T = k.size(1), H = k.size(2), D = k.size(3);
+    TORCH_CHECK(kc.size(1) == H && kc.size(3) == D && kc.device() == k.device(), "cache / new kv mismatch");
+    TORCH_CHECK(pos.scalar_type() == at::kInt && pos.numel() == B, "pos must be int32 [B]");
+    const int* ci = nullptr;
+    if (cache_idx.has_value()) {
+      TORCH_CHECK(cache_idx->scalar_type() == at::kInt && cache_idx->numel() == B, "cache_idx must be int32 [B]");
+      ci = cache_idx->data_ptr<int>();
+    } else {
+      TORCH_CHECK(kc.size(0) >= B, "cache batch too small");
+    }
+    check_rc(nxd::kv_write_mx8_launch(k.data_ptr(), v.data_ptr(), ks, kc.data_ptr(), vc.data_ptr(), k_scale->data_ptr(),
+                                      v_scale->data_ptr(), ci, pos.data_ptr<int>(), B, (int)kc.size(0), T, H, D, (int)kc.size(2),
+                                      cur_stream()),
+             "kv_write_mx8");
+    return;
+  }
   check_bf16(kc, "k_cache");
   check_bf16(vc, "v_cache");
   TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.sizes() == kc.sizes() && vc.is_contiguous(), "bad caches");
@@ -1241,14 +1356,17 @@ PYBIND11_MODULE(_C, m) {
   m.def("embedding_bwd", &embedding_bwd);
   // window: sliding-window attention, a query sees itself and the window - 1 keys before it (0 = none)
   m.def("decode_attn", &decode_attn, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cache_idx"),
-        py::arg("seq_len"), py::arg("out"), py::arg("scale"), py::arg("nsplit"), py::arg("window") = 0);
+        py::arg("seq_len"), py::arg("out"), py::arg("scale"), py::arg("nsplit"), py::arg("window") = 0,
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("decode_attn_oproj", &decode_attn_oproj, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cache_idx"),
         py::arg("seq_len"), py::arg("wo"), py::arg("oacc"), py::arg("scale"), py::arg("window") = 0);
   m.def("decode_attn_sync_error", [](bool reset) { return nxd::decode_attn_sync_error(reset); }, py::arg("reset") = false);
   m.def("decode_attn_set_sync", [](int64_t v) { nxd::decode_attn_set_sync((int)v); });
   m.def("decode_attn_set_oproj_maxl", [](int64_t v) { nxd::decode_attn_set_oproj_maxl((int)v); });
   m.def("decode_attn_prefetch", &decode_attn_prefetch);
-  m.def("kv_cache_write", &kv_cache_write);
+  m.def("kv_cache_write", &kv_cache_write, py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("cache_idx"), py::arg("pos"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+  m.def("mx8_dequant", &mx8_dequant);
   m.def("argmax_rows", &argmax_rows);
   m.def("greedy_advance", &greedy_advance);
   m.def("topk_sample", &topk_sample);

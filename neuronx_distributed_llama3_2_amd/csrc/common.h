@@ -35,6 +35,10 @@ __device__ __forceinline__ uint32_t pack2bf(float lo, float hi) {
   return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
 }
 
+// E8M0 block-scale byte -> the f32 whose exponent field it is (2^(e-127) for e in 1..254): the scale
+// operand of gfx950's v_cvt_scalef32_* converts (MXFP4 weights, MXFP8 KV cache)
+__device__ __forceinline__ float e8m0(uint8_t e) { return __uint_as_float((uint32_t)e << 23); }
+
 // 8 bf16 <-> 8 floats through one 16-byte vector.
 __device__ __forceinline__ void unpack8(const u32x4_t& v, float* f) {
 #pragma unroll

@@ -80,6 +80,11 @@ struct Params {
   // launchers size kps / nsplit by the window, not the cache (window_span).  Value-initialised to 0
   // by every launcher, as the rule above asks.
   int window;
+  // KV8 (MXFP8 cache, ops/decode.py): kc / vc are E4M3 code bytes (c_sb / c_sh / c_sl in bytes) and these
+  // the E8M0 block-scale bytes [Bc, Hkv, Lmax, D / 32] with their strides; null for a bf16 cache.
+  const uint8_t* ksc;
+  const uint8_t* vsc;
+  int64_t s_sb, s_sh, s_sl;
 };
 static_assert(std::is_trivially_copyable<Params>::value && sizeof(Params) <= 4096, "kernel-argument struct");
 
@@ -109,6 +114,13 @@ __device__ __forceinline__ void prefetch_body(const Params& p, int wg, int nwg) 
 }
 
 typedef __attribute__((address_space(3))) short4_t lds_s4_t;
+
+// KV8: two E4M3 codes (the low or high half of a dword) times the block scale -> one dword of two bf16
+template <typename B>
+__device__ __forceinline__ uint32_t cvt2_fp8_t(uint32_t codes, float scale, B) {
+  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(codes, scale, B::value));
+}
+#define cvt2_fp8(codes, scale, hi) cvt2_fp8_t(codes, scale, std::integral_constant<bool, hi>{})
 typedef short short8_t __attribute__((ext_vector_type(8)));
 
 // FUSE o_proj pieces: thread (row row0 + pass * rpp, 32-column segment) holds its Wo block in
@@ -164,13 +176,23 @@ __device__ __forceinline__ void oproj_tail(const Params& p, const float* of, con
 // more than a kernel boundary, so it is off by default (NXD_DECODE_ATTN_SYNC=1).
 // WIN: sliding window (Params::window > 0).  A template flag, not a run-time test, so that the
 // un-windowed instantiations keep the code they had.
-template <int D, int NWV, bool FUSE, bool WO_LATE = true, bool SYNC = false, bool WIN = false>
+// KV8: MXFP8 cache (Params::ksc / vsc), likewise a template flag.  Only the loads differ: lane (mi, g)
+// loads the 8 code bytes of its K fragment (one block, so one scale) and the key's D / 32 scale bytes
+// in one 2- or 4-byte load; a V load is 16 codes of one block plus its scale byte.  K is converted to
+// the bf16 MFMA operand (v_cvt_scalef32_pk_bf16_fp8, exact) right before the score MFMA and V on its way
+// into the same bf16 LDS tile, so the transposed reads, the softmax, P.V and the merge see the values a
+// bf16 cache holding the dequantized data would give them, in the same order: the outputs are equal
+// bit for bit.
+template <int D, int NWV, bool FUSE, bool WO_LATE = true, bool SYNC = false, bool WIN = false, bool KV8 = false>
 __global__ void __launch_bounds__(64 * NWV) attn_kernel(Params p) {
   static_assert(!SYNC || FUSE, "SYNC is a FUSE form");
   static_assert(!WIN || !SYNC, "no SYNC form with a sliding window");
+  static_assert(!KV8 || !FUSE, "the fused attention + o_proj reads a bf16 cache");
   constexpr int NS = D / 32;      // k-steps of the score MFMA
   constexpr int NDT = D / 16;     // 16-wide d tiles of the output
   constexpr int VL = D / 8;       // 16-B V loads per lane for 64 keys x D
+  constexpr int VL8 = D / 16;     // KV8: 16-B loads of 16 codes
+  using kscale_t = std::conditional_t<D == 64, uint16_t, uint32_t>;   // a key's D / 32 scale bytes
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int mi = lane & 15, g = lane >> 4;
@@ -227,18 +249,43 @@ __global__ void __launch_bounds__(64 * NWV) attn_kernel(Params p) {
   // FUSE: the whole cache in one pass per workgroup (no key splits, no merge launch)
   const int kend = (FUSE && !SYNC) ? slen : min(slen, kbeg + (split + 1) * p.kps);
   // K fragments and the V chunk of the NEXT chunk are loaded while this one runs its softmax and P.V
-  u32x4_t kf[4][NS], vv[VL];
+  u32x4_t kf[KV8 ? 1 : 4][KV8 ? 1 : NS], vv[KV8 ? VL8 : VL];
+  u32x2_t kf8[KV8 ? 4 : 1][KV8 ? NS : 1];   // KV8: 8 codes per fragment,
+  kscale_t ksb[4];                           //      each key tile's scale bytes,
+  uint8_t vsb[VL8];                          //      the scale byte of each V load
+  const uint8_t* kbase8 = reinterpret_cast<const uint8_t*>(p.kc) + (int64_t)cb * p.c_sb + (int64_t)hkv * p.c_sh;
+  const uint8_t* vbase8 = reinterpret_cast<const uint8_t*>(p.vc) + (int64_t)cb * p.c_sb + (int64_t)hkv * p.c_sh;
+  const uint8_t* ksbase = p.ksc + (int64_t)cb * p.s_sb + (int64_t)hkv * p.s_sh;
+  const uint8_t* vsbase = p.vsc + (int64_t)cb * p.s_sb + (int64_t)hkv * p.s_sh;
   auto load_chunk = [&](int k0) {
+    if constexpr (KV8) {
 #pragma unroll
-    for (int i = 0; i < VL; ++i) {
-      const int idx = lane + 64 * i, key = idx / (D / 8), c = idx % (D / 8);
-      vv[i] = *reinterpret_cast<const u32x4_t*>(vbase + (int64_t)min(k0 + key, slen - 1) * p.c_sl + 8 * c);
-    }
+      for (int i = 0; i < VL8; ++i) {
+        const int idx = lane + 64 * i, key = idx / (D / 16), c = idx % (D / 16);
+        const int64_t row = min(k0 + key, slen - 1);
+        vv[i] = *reinterpret_cast<const u32x4_t*>(vbase8 + row * p.c_sl + 16 * c);
+        vsb[i] = vsbase[row * p.s_sl + c / 2];
+      }
 #pragma unroll
-    for (int kt = 0; kt < 4; ++kt) {
-      const uint16_t* kr = kbase + (int64_t)min(k0 + kt * 16 + mi, slen - 1) * p.c_sl + 8 * g;
+      for (int kt = 0; kt < 4; ++kt) {
+        const int64_t row = min(k0 + kt * 16 + mi, slen - 1);
+        const uint8_t* kr = kbase8 + row * p.c_sl + 8 * g;
 #pragma unroll
-      for (int s = 0; s < NS; ++s) kf[kt][s] = *reinterpret_cast<const u32x4_t*>(kr + 32 * s);
+        for (int s = 0; s < NS; ++s) kf8[kt][s] = *reinterpret_cast<const u32x2_t*>(kr + 32 * s);
+        ksb[kt] = *reinterpret_cast<const kscale_t*>(ksbase + row * p.s_sl);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < VL; ++i) {
+        const int idx = lane + 64 * i, key = idx / (D / 8), c = idx % (D / 8);
+        vv[i] = *reinterpret_cast<const u32x4_t*>(vbase + (int64_t)min(k0 + key, slen - 1) * p.c_sl + 8 * c);
+      }
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        const uint16_t* kr = kbase + (int64_t)min(k0 + kt * 16 + mi, slen - 1) * p.c_sl + 8 * g;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) kf[kt][s] = *reinterpret_cast<const u32x4_t*>(kr + 32 * s);
+      }
     }
   };
   int k0 = kbeg + split * p.kps + wid * KB;
@@ -255,15 +302,39 @@ __global__ void __launch_bounds__(64 * NWV) attn_kernel(Params p) {
     for (int kt = 0; kt < 4; ++kt) {
       sc[kt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int s = 0; s < NS; ++s)
-        sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, kf[kt][s]), qf[s], sc[kt], 0, 0, 0);
+      for (int s = 0; s < NS; ++s) {
+        bf16x8_t ka;
+        if constexpr (KV8) {
+          const float ksf = e8m0((uint8_t)(ksb[kt] >> (8 * s)));
+          const u32x4_t kw = {cvt2_fp8(kf8[kt][s][0], ksf, false), cvt2_fp8(kf8[kt][s][0], ksf, true),
+                              cvt2_fp8(kf8[kt][s][1], ksf, false), cvt2_fp8(kf8[kt][s][1], ksf, true)};
+          ka = __builtin_bit_cast(bf16x8_t, kw);
+        } else {
+          ka = __builtin_bit_cast(bf16x8_t, kf[kt][s]);
+        }
+        sc[kt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qf[s], sc[kt], 0, 0, 0);
+      }
     }
     // V tile -> LDS (row-major [key][D]) once the wave's previous transposed reads have retired
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if constexpr (KV8) {
 #pragma unroll
-    for (int i = 0; i < VL; ++i) {
-      const int idx = lane + 64 * i, key = idx / (D / 8), c = idx % (D / 8);
-      *reinterpret_cast<u32x4_t*>(vt + key * D + 8 * c) = vv[i];
+      for (int i = 0; i < VL8; ++i) {
+        const int idx = lane + 64 * i, key = idx / (D / 16), c = idx % (D / 16);
+        const float vsf = e8m0(vsb[i]);
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+          const u32x4_t w = {cvt2_fp8(vv[i][2 * hf], vsf, false), cvt2_fp8(vv[i][2 * hf], vsf, true),
+                             cvt2_fp8(vv[i][2 * hf + 1], vsf, false), cvt2_fp8(vv[i][2 * hf + 1], vsf, true)};
+          *reinterpret_cast<u32x4_t*>(vt + key * D + 16 * c + 8 * hf) = w;
+        }
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < VL; ++i) {
+        const int idx = lane + 64 * i, key = idx / (D / 8), c = idx % (D / 8);
+        *reinterpret_cast<u32x4_t*>(vt + key * D + 8 * c) = vv[i];
+      }
     }
     if (k0 + NWV * KB < kend) load_chunk(k0 + NWV * KB);
     // ---- online softmax of query row mi over this chunk: lane holds keys k0 + 16 kt + 4 g + v
@@ -641,13 +712,23 @@ void decode_attn_set_prefetch(const void* a, int64_t a_bytes, const void* b, int
 
 // Returns -1 when the shape is not covered (caller falls back to the 128-key-chunk kernel).
 // window > 0: sliding-window attention (Params::window); kps / nsplit follow the window's key span.
+// ksc / vsc non-null: MXFP8 cache (KV8) -- kc / vc are the code bytes with byte strides cs (16-byte
+// aligned rows), ksc / vsc the scale bytes with strides ss (rows aligned to their D / 32 bytes).
 int decode_attn2_launch(const void* q, const int64_t* qs, const void* kc, const void* vc, const int64_t* cs,
                         const int* cache_idx, const int* seq_len, float* po, float* pm, float* pl, void* out,
                         const int64_t* os, int B, int T, int Hq, int Hkv, int D, int Lmax, float scale, int* nsplit_out,
-                        hipStream_t stream, int window) {
+                        hipStream_t stream, int window, const void* ksc, const void* vsc, const int64_t* ss) {
   if (Hkv <= 0 || Hq % Hkv) return -1;
   const int M = (Hq / Hkv) * T;
   if (M > 16 || (D != 64 && D != 128)) return -1;
+  if ((ksc != nullptr) != (vsc != nullptr)) return -1;
+  if (ksc != nullptr) {
+    const auto al = [](const void* a, int64_t n) { return reinterpret_cast<uintptr_t>(a) % n == 0; };
+    const int sb = D / 32;
+    if (ss == nullptr || !al(kc, 16) || !al(vc, 16) || cs[0] % 16 || cs[1] % 16 || cs[2] % 16 || !al(ksc, sb) || !al(vsc, sb) ||
+        ss[0] % sb || ss[1] % sb || ss[2] % sb)
+      return -1;
+  }
   const int Leff = dattn::window_span(Lmax, T, window);
   dattn::Params p{};   // value-initialised: every field a launcher does not set is zero / null
   p.q = (const uint16_t*)q; p.q_sb = qs[0]; p.q_st = qs[1]; p.q_sh = qs[2];
@@ -679,7 +760,23 @@ int decode_attn2_launch(const void* q, const int64_t* qs, const void* kc, const 
   dattn::g_pf[0] = dattn::g_pf[1] = nullptr;
   dattn::g_pf_bytes[0] = dattn::g_pf_bytes[1] = 0;
   const dim3 grid(p.attn_wgs + pf_wgs), block(64 * nwv);
-  if (window) {
+  if (ksc != nullptr) {   // MXFP8 cache: the KV8 instantiations (same LDS as the bf16 ones)
+    p.ksc = (const uint8_t*)ksc; p.vsc = (const uint8_t*)vsc;
+    p.s_sb = ss[0]; p.s_sh = ss[1]; p.s_sl = ss[2];
+    if (window && D == 64) {
+      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, false, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((dattn::attn_kernel<64, 8, false, true, false, true, true>), grid, block, lds, stream, p);
+    } else if (window) {
+      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<128, 4, false, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((dattn::attn_kernel<128, 4, false, true, false, true, true>), grid, block, lds, stream, p);
+    } else if (D == 64) {
+      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, false, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((dattn::attn_kernel<64, 8, false, true, false, false, true>), grid, block, lds, stream, p);
+    } else {
+      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<128, 4, false, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((dattn::attn_kernel<128, 4, false, true, false, false, true>), grid, block, lds, stream, p);
+    }
+  } else if (window) {
     if (D == 64) {
       (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       hipLaunchKernelGGL((dattn::attn_kernel<64, 8, false, true, false, true>), grid, block, lds, stream, p);
@@ -815,7 +912,7 @@ int decode_attn_oproj_launch(const void* q, const int64_t* qs, const void* kc, c
     int ns2 = 0;
     const int64_t no_out[3] = {0, 0, 0};
     const int rc = decode_attn2_launch(q, qs, kc, vc, cs, cache_idx, seq_len, po, pm, pl, nullptr, no_out, B, T, Hq, Hkv,
-                                       D, Lcache, scale, &ns2, stream, window);
+                                       D, Lcache, scale, &ns2, stream, window, nullptr, nullptr, nullptr);
     if (rc != 0) return rc;
     if (ns2 != ns) return 3;   // the attention launch split differently: never write the output through null
     p.nsplit = ns; p.po = po; p.pm = pm; p.pl = pl;

@@ -34,9 +34,6 @@ struct Params {
 static_assert(std::is_trivially_copyable<Params>::value && sizeof(Params) <= 4096, "kernel-argument struct");
 static_assert(sizeof(Params) == 88 && alignof(Params) == 8, "Params layout: nine 8-byte fields, M / N / K, tail padding");
 
-// E8M0 byte -> the f32 whose exponent field it is (2^(e-127) for e in 1..254)
-__device__ __forceinline__ float e8m0(uint8_t e) { return __uint_as_float((uint32_t)e << 23); }
-
 // 8 codes of one dword (element 2j = low nibble of byte j) times the block scale -> 4 bf16 pairs
 struct W8 {
   bf16x2_t p[4];

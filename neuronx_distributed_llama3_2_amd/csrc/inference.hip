@@ -526,7 +526,7 @@ __global__ void __launch_bounds__(1024) topk_sample_kernel(const T* __restrict__
 
 int decode_attn2_launch(const void*, const int64_t*, const void*, const void*, const int64_t*, const int*, const int*,
                         float*, float*, float*, void*, const int64_t*, int, int, int, int, int, int, float, int*, hipStream_t,
-                        int);
+                        int, const void*, const void*, const int64_t*);
 
 static int g_attn_v2 = [] { const char* e = getenv("NXD_DECODE_ATTN_V2"); return e ? atoi(e) : 1; }();
 void decode_attn_set_v2(int v) { g_attn_v2 = v; }
@@ -534,16 +534,21 @@ void decode_attn_set_v2(int v) { g_attn_v2 = v; }
 int decode_attn_launch(const void* q, const int64_t* qs, const void* kc, const void* vc, const int64_t* cs,
                        const int* cache_idx, const int* seq_len, float* po, float* pm, float* pl, int* counters, void* out,
                        const int64_t* os, int B, int T, int Hq, int Hkv, int D, int nsplit, float scale, hipStream_t stream,
-                       int window) {
+                       int window, const void* ksc, const void* vsc, const int64_t* ss) {
   using namespace dec;
   if (Hkv <= 0 || Hq % Hkv) return -1;
   const int M = (Hq / Hkv) * T;
   if (window < 0 || window >= nsplit * kChunk) window = 0;   // covers the cache: no window
+  // MXFP8 cache (ksc / vsc: the scale bytes, kc / vc the codes): only the MFMA kernel reads it; -4 tells
+  // the caller to dequantize (mx8_dequant) and come back with a bf16 cache
+  const bool kv8 = ksc != nullptr || vsc != nullptr;
+  if (kv8 && !g_attn_v2) return -4;
   // small query groups: the MFMA flash-decoding kernel (decode_attn.hip), merge only past 1024 keys
   if (g_attn_v2) {
     int ns2 = 0;
     const int rc = decode_attn2_launch(q, qs, kc, vc, cs, cache_idx, seq_len, po, pm, pl, out, os, B, T, Hq, Hkv, D,
-                                       nsplit * kChunk, scale, &ns2, stream, window);
+                                       nsplit * kChunk, scale, &ns2, stream, window, ksc, vsc, ss);
+    if (kv8 && rc == -1) return -4;
     if (rc == 0 && ns2 > 1) {
       DecodeParams mp{};
       mp.q = (const uint16_t*)q; mp.q_sb = qs[0]; mp.q_st = qs[1]; mp.q_sh = qs[2];

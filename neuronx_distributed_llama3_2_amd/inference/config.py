@@ -20,6 +20,9 @@ from typing import Any, Dict, List, Optional
 from .bucketing import generate_buckets
 
 
+KV_CACHE_DTYPES = (None, "bfloat16", "mxfp8")
+
+
 class InferenceConfig:
     def __init__(self, tp_degree: int = 1, batch_size: int = 1, seq_len: int = 128, padding_side: str = "right",
                  **kwargs):
@@ -46,6 +49,11 @@ class InferenceConfig:
         self.quantized_checkpoints_path = kwargs.pop("quantized_checkpoints_path", None)
         # "per_tensor_symmetric" / "per_channel_symmetric" (int8) or "mxfp4" (block-scaled 4-bit)
         self.quantization_type = kwargs.pop("quantization_type", "per_tensor_symmetric")
+        # KV-cache storage: None / "bfloat16" (the activation dtype) or "mxfp8" (E4M3 codes + E8M0 block
+        # scales, 33/64 of the bytes; format in ops/decode.py)
+        self.kv_cache_dtype = kwargs.pop("kv_cache_dtype", None)
+        if self.kv_cache_dtype not in KV_CACHE_DTYPES:
+            raise ValueError(f"kv_cache_dtype must be one of {KV_CACHE_DTYPES}, got {self.kv_cache_dtype!r}")
         self.trace_tokengen_model = kwargs.pop("trace_tokengen_model", True)
         self.speculation_length = kwargs.pop("speculation_length", 0)
         self.spec_rounds_per_graph = kwargs.pop("spec_rounds_per_graph", 4)

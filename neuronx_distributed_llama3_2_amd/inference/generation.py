@@ -179,6 +179,8 @@ class LlamaForCausalLMInference:
                                      device=torch.device("meta") if not init_weights else self.device)
         # InferenceConfig(deterministic=True): no fp32-atomic fused decode launches (model_base.py)
         self.model._decode_deterministic = bool(getattr(config, "deterministic", False))
+        # InferenceConfig(kv_cache_dtype="mxfp8"): setup_kv_cache allocates codes + block scales
+        self.model._kv_cache_dtype = getattr(config, "kv_cache_dtype", None)
         if config.quantized:
             self._quantize()
         self.max_batch = config.max_batch_size

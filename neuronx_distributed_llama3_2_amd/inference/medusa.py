@@ -97,6 +97,8 @@ class MedusaDecoder:
         if 0 < window < target.cache_len:
             raise NotImplementedError(f"Medusa tree verification does not apply the model's sliding window ({window} "
                                       f"keys, shorter than the {target.cache_len}-key cache)")
+        if getattr(target.model, "_kv_cache_dtype", None) == "mxfp8":
+            raise NotImplementedError("Medusa tree verification reads a bf16 KV cache; kv_cache_dtype='mxfp8' is not supported")
         bufs = medusa_tree_buffers(choices or DEFAULT_MEDUSA_CHOICES, topk)
         dev = target.device
         self.mask = bufs["attn_mask"].to(dev).bool()

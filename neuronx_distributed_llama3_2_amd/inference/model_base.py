@@ -72,6 +72,7 @@ class DecoderInferenceMixin:
         self.nq, self.nkv, self.head_dim = attn0.num_heads_local, attn0.num_kv_heads_local, attn0.head_dim
         self.tp = get_tensor_model_parallel_size()
         self.kv_cache: Optional[torch.Tensor] = None
+        self.kv_cache_scale: Optional[torch.Tensor] = None   # MXFP8 cache only (setup_kv_cache)
         self.eps = float(config.rms_norm_eps)
         # a query sees itself and the sliding_window - 1 keys before it; 0: every earlier key
         self.sliding_window = int(getattr(config, "sliding_window", None) or 0)
@@ -86,13 +87,34 @@ class DecoderInferenceMixin:
         device = device or emb.device
         L = len(self.model.layers)
         shape = (L, 2, max_batch, self.nkv, max_len, self.head_dim)
-        if self.kv_cache is None or tuple(self.kv_cache.shape) != shape or self.kv_cache.device != torch.device(device):
-            self.kv_cache = torch.zeros(shape, dtype=emb.dtype, device=device)
+        quant = self._kv_quantized()
+        dtype = torch.uint8 if quant else emb.dtype
+        if quant and self.head_dim % ops.decode.MX8_BLOCK:
+            raise ValueError(f"kv_cache_dtype='mxfp8' needs head_dim % {ops.decode.MX8_BLOCK} == 0, got {self.head_dim}")
+        if (self.kv_cache is None or tuple(self.kv_cache.shape) != shape or self.kv_cache.device != torch.device(device)
+                or self.kv_cache.dtype != dtype):
+            self.kv_cache = torch.zeros(shape, dtype=dtype, device=device)
+            # MXFP8 (ops/decode.py): E4M3 codes above, one E8M0 scale byte per 32 elements of a head vector here
+            self.kv_cache_scale = torch.zeros(shape[:-1] + (self.head_dim // ops.decode.MX8_BLOCK,), dtype=torch.uint8,
+                                              device=device) if quant else None
+            self._decode_fused_ok = None   # the fused decode launches read and write a bf16 cache
         return self.kv_cache
 
     def reset_kv_cache(self) -> None:
         if self.kv_cache is not None:
             self.kv_cache.zero_()
+        if getattr(self, "kv_cache_scale", None) is not None:
+            self.kv_cache_scale.zero_()   # code 0 is 0 under any scale
+
+    def _kv_quantized(self) -> bool:
+        """True when the application asked for an MXFP8 KV cache (InferenceConfig.kv_cache_dtype)."""
+        return getattr(self, "_kv_cache_dtype", None) == "mxfp8"
+
+    def _layer_cache(self, i: int):
+        """(k cache, v cache, {k_scale, v_scale} for an MXFP8 cache else {}) of layer i."""
+        kc, vc = self.kv_cache[i, 0], self.kv_cache[i, 1]
+        sc = getattr(self, "kv_cache_scale", None)
+        return kc, vc, ({} if sc is None else {"k_scale": sc[i, 0], "v_scale": sc[i, 1]})
 
     # ------------------------------------------------------------------ sliding window
     def _decode_window(self) -> int:
@@ -158,12 +180,12 @@ class DecoderInferenceMixin:
             q = qkv.view(B, T, nq + 2 * nkv, D)[:, :, :nq]
             k = qkv.view(B, T, nq + 2 * nkv, D)[:, :, nq:nq + nkv]
             v = qkv.view(B, T, nq + 2 * nkv, D)[:, :, nq + nkv:]
-            kc, vc = self.kv_cache[i, 0], self.kv_cache[i, 1]
-            ops.kv_cache_write(k, v, kc, vc, pos0, sid32)
-            if prefill:
+            kc, vc, sc = self._layer_cache(i)
+            ops.kv_cache_write(k, v, kc, vc, pos0, sid32, **sc)
+            if prefill:   # over the new (unquantized) K/V: only the cache write quantizes
                 o, _ = ops.flash_attn_fwd_lse(q, k, v, causal=True, key_ranges=win_ranges)
             else:
-                o = ops.decode_attention(q, kc, vc, cache_len, sid32, window=window)
+                o = ops.decode_attention(q, kc, vc, cache_len, sid32, window=window, **sc)
             x = self._row(attn.o_proj, o.reshape(B, T, nq * D))
             h, residual = self._norm(x, layer.post_attention_layernorm.weight, residual)
             x = self._ffn(layer, h)
@@ -191,6 +213,10 @@ class DecoderInferenceMixin:
 
     def _check_decode_fusable(self) -> bool:
         if os.environ.get("NXD_DECODE_FUSED", "1") == "0":
+            return False
+        if self._kv_quantized():
+            # the fused QKV epilogue writes bf16 cache elements (one output row per wave) and the fused
+            # attention + o_proj reads bf16: an MXFP8 cache decodes on the unfused launches
             return False
         if self.tp > 1 and os.environ.get("NXD_DECODE_FUSED_TP", "1") == "0":
             return False
@@ -407,6 +433,8 @@ class DecoderInferenceMixin:
         the caller commits only the accepted path (commit_tree_kv)."""
         if self._decode_window():
             raise NotImplementedError("tree verification does not apply config.sliding_window")
+        if self._kv_quantized():
+            raise NotImplementedError("tree verification reads a bf16 KV cache; kv_cache_dtype='mxfp8' is not supported")
         N = tokens.shape[0]
         nq, nkv, D = self.nq, self.nkv, self.head_dim
         g = nq // nkv
@@ -450,8 +478,9 @@ class DecoderInferenceMixin:
         sid = torch.tensor([seq_id], dtype=torch.int32, device=nodes.device)
         pos = torch.tensor([start], dtype=torch.int32, device=nodes.device)
         for i, (k, v) in enumerate(kvs):
+            kc, vc, sc = self._layer_cache(i)
             ops.kv_cache_write(k.index_select(0, nodes).unsqueeze(0), v.index_select(0, nodes).unsqueeze(0),
-                               self.kv_cache[i, 0], self.kv_cache[i, 1], pos, sid)
+                               kc, vc, pos, sid, **sc)
 
     def _row(self, mod, x: torch.Tensor) -> torch.Tensor:
         """Row-parallel projection: partial GEMM, TP all-reduce, then the (replicated) bias."""

@@ -4,8 +4,8 @@ PyTorch fp32 reference on the CPU (see _ext.use_native)."""
 from ._ext import ext, ext_available, use_native  # noqa: F401
 from .activations import swiglu, swiglu_reference  # noqa: F401
 from .cross_entropy import parallel_cross_entropy_reference, vocab_parallel_cross_entropy  # noqa: F401
-from .decode import (argmax_rows, decode_attention, decode_window, greedy_advance_, kv_cache_write,  # noqa: F401
-                     topk_sample)
+from .decode import (argmax_rows, decode_attention, decode_window, dequantize_mxfp8, greedy_advance_,  # noqa: F401
+                     kv_cache_write, quantize_mxfp8, topk_sample)
 from .embedding import vocab_parallel_embedding  # noqa: F401
 from .grouped_gemm import (grouped_linear, grouped_linear_reference, moe_dispatch, moe_permutation,  # noqa: F401
                            moe_unpermute_combine)
