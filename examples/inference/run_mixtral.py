@@ -5,6 +5,8 @@ mixtral/mixtral_runner.py).  Same modes and flags as llama3_2_runner.py:
     python examples/inference/run_mixtral.py generate --traced_path out --prompt_ids 1,2,3
 TP > 1: `torchrun --nproc-per-node N ... --tp_degree N`; experts are TP-sharded on the
 intermediate dim, token generation reads only the routed experts' weights.
+`trace ... --quantized --quantization_type mxfp4` stores o_proj, the lm_head and the experts as MXFP4
+(4.25 bits per weight); `generate` on that directory reads the packed shards.
 """
 
 import os

@@ -67,6 +67,8 @@ int mx_gemv_launch(const void*, int64_t, const void*, int64_t, const void*, int6
                    int, int, hipStream_t);
 int mx_gemv_rows_per_wave(int, int);
 int mx_dequant_launch(const void*, int64_t, const void*, int64_t, void*, int, int, hipStream_t);
+int mx_expert_gemv_launch(const void*, int64_t, int64_t, const void*, int64_t, int64_t, const void*, int64_t, int64_t,
+                          const int32_t*, int, int, int, void*, int64_t, int64_t, int, int, int, int, hipStream_t);
 int expert_gemv_launch(const void*, int64_t, const void*, int64_t, int64_t, const int32_t*, int, int, void*, int64_t, int,
                        int, int, hipStream_t);
 void dgemv_set_knob(int, int);
@@ -925,6 +927,75 @@ void mx_gemv(at::Tensor x, at::Tensor w, at::Tensor scale, c10::optional<at::Ten
            "mx_gemv");
 }
 
+// MXFP4 expert stack: packed uint8 [E, Nw, K/2] + E8M0 scale uint8 [E, Nw, K/32], unit inner strides, 16-byte
+// aligned code rows and expert stride
+static void check_mx_stack(const at::Tensor& w, const at::Tensor& scale, int64_t K, int64_t Nw, const char* op) {
+  check_cuda(w, "w");
+  check_cuda(scale, "scale");
+  TORCH_CHECK(w.scalar_type() == at::kByte && scale.scalar_type() == at::kByte, op, ": packed weight and scale must be uint8");
+  TORCH_CHECK(w.dim() == 3 && scale.dim() == 3 && w.stride(2) == 1 && scale.stride(2) == 1, op,
+              ": 3-D weight / scale with unit inner strides");
+  TORCH_CHECK(K >= 32 && K % 32 == 0 && w.size(2) == K / 2 && scale.size(2) == K / 32 && scale.size(0) == w.size(0) &&
+                  scale.size(1) == w.size(1) && w.size(0) >= 1,
+              op, ": weight [E, Nw, K/2] and scale [E, Nw, K/32] with K a multiple of 32");
+  TORCH_CHECK(w.size(1) == Nw && Nw >= 1, op, ": weight shape mismatch");
+  TORCH_CHECK(w.stride(1) % 16 == 0 && w.stride(0) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, op,
+              ": 16-byte aligned weight rows and expert stride required");
+  TORCH_CHECK(w.stride(1) >= K / 2 && w.stride(0) >= 0 && scale.stride(1) >= K / 32 && scale.stride(0) >= 0, op,
+              ": weight / scale rows must not overlap");
+  TORCH_CHECK(w.device() == scale.device(), op, ": weight and scale on different devices");
+}
+
+// selective MoE decode: y[p, :N] = x[p / xdiv] . deq(W[eidx[p]])^T; x [X, K] bf16, eidx [P] int32, y [P, N]
+void mx_expert_gemv(at::Tensor x, at::Tensor w, at::Tensor scale, at::Tensor eidx, int64_t xdiv, at::Tensor y, bool glu) {
+  check_cuda(x, "x");
+  check_bf16(x, "x");
+  check_cuda(y, "y");
+  check_bf16(y, "y");
+  check_cuda(eidx, "eidx");
+  TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && x.stride(1) == 1 && y.stride(1) == 1,
+              "mx_expert_gemv: 2-D x / y, unit inner strides");
+  TORCH_CHECK(eidx.scalar_type() == at::kInt && eidx.dim() == 1 && eidx.is_contiguous(), "mx_expert_gemv: eidx int32 [P]");
+  const int64_t P = eidx.size(0), K = x.size(1), N = y.size(1);
+  check_mx_stack(w, scale, K, glu ? 2 * N : N, "mx_expert_gemv");
+  TORCH_CHECK(xdiv >= 1 && y.size(0) == P && (P + xdiv - 1) / xdiv <= x.size(0), "mx_expert_gemv: x/y rows vs pairs");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && x.stride(0) >= K && y.stride(0) >= N &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "mx_expert_gemv: 16-byte aligned activation rows required");
+  TORCH_CHECK(x.device() == w.device() && y.device() == w.device() && eidx.device() == w.device(),
+              "mx_expert_gemv: operands on different devices");
+  TORCH_CHECK(P <= 65535, "mx_expert_gemv: too many pairs");
+  if (P == 0) return;
+  check_rc(nxd::mx_expert_gemv_launch(x.data_ptr(), x.stride(0), x.stride(0), w.data_ptr(), w.stride(1), w.stride(0),
+                                      scale.data_ptr(), scale.stride(1), scale.stride(0), eidx.data_ptr<int32_t>(),
+                                      (int)w.size(0), (int)P, (int)xdiv, y.data_ptr(), y.stride(0), y.stride(0), 1, (int)N,
+                                      (int)K, glu, cur_stream()),
+           "mx_expert_gemv");
+}
+
+// every expert, M <= 8 rows: y[e, m, :N] = x[(e,) m] . deq(W[e])^T; x [M, K] (shared) or [E, M, K], y [E, M, N]
+void mx_experts_gemv(at::Tensor x, at::Tensor w, at::Tensor scale, at::Tensor y, bool glu) {
+  check_cuda(x, "x");
+  check_bf16(x, "x");
+  check_cuda(y, "y");
+  check_bf16(y, "y");
+  TORCH_CHECK((x.dim() == 2 || x.dim() == 3) && y.dim() == 3 && x.stride(-1) == 1 && y.stride(2) == 1,
+              "mx_experts_gemv: x [M, K] or [E, M, K], y [E, M, N], unit inner strides");
+  const int64_t E = y.size(0), M = y.size(1), N = y.size(2), K = x.size(-1);
+  check_mx_stack(w, scale, K, glu ? 2 * N : N, "mx_experts_gemv");
+  TORCH_CHECK(w.size(0) == E && E <= 65535, "mx_experts_gemv: y [E, M, N] against E experts");
+  TORCH_CHECK(M >= 1 && M <= 8 && x.size(-2) == M && (x.dim() == 2 || x.size(0) == E), "mx_experts_gemv: 1 <= M <= 8 rows");
+  const int64_t ldx = x.stride(-2), xps = x.dim() == 3 ? x.stride(0) : 0;
+  TORCH_CHECK(ldx % 8 == 0 && xps % 8 == 0 && ldx >= K && xps >= 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "mx_experts_gemv: 16-byte aligned activation rows required");
+  TORCH_CHECK(y.stride(1) >= N && y.stride(0) >= M * y.stride(1), "mx_experts_gemv: y rows must not overlap");
+  TORCH_CHECK(x.device() == w.device() && y.device() == w.device(), "mx_experts_gemv: operands on different devices");
+  check_rc(nxd::mx_expert_gemv_launch(x.data_ptr(), ldx, xps, w.data_ptr(), w.stride(1), w.stride(0), scale.data_ptr(),
+                                      scale.stride(1), scale.stride(0), nullptr, (int)E, (int)E, 1, y.data_ptr(), y.stride(1),
+                                      y.stride(0), (int)M, (int)N, (int)K, glu, cur_stream()),
+           "mx_experts_gemv");
+}
+
 void mx_dequant(at::Tensor w, at::Tensor scale, at::Tensor out) {
   check_bf16(out, "out");
   check_cuda(out, "out");
@@ -1271,6 +1342,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("expert_gemv", &expert_gemv);
   m.def("mx_gemv", &mx_gemv);
   m.def("mx_dequant", &mx_dequant);
+  m.def("mx_expert_gemv", &mx_expert_gemv);
+  m.def("mx_experts_gemv", &mx_experts_gemv);
   m.def("mx_gemv_rows_per_wave", [](int64_t N, int64_t K) { return nxd::mx_gemv_rows_per_wave((int)N, (int)K); });
   m.def("grouped_gemm", &grouped_gemm);
   m.def("wgrad_gemm", &wgrad_gemm);

@@ -57,70 +57,33 @@ __device__ __forceinline__ float dot8(const u32x4_t& x, const W8& w, float acc) 
 
 template <int MM, int ROWS, bool GLU>
 __global__ void __launch_bounds__(256) mx_gemv_kernel(Params p) {
-  constexpr int NW = GLU ? 2 * ROWS : ROWS;  // weight rows per wave
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * 4) + (threadIdx.x >> 6);
-  const int n0 = wave * ROWS;
-  if (n0 >= p.N) return;
-  int wrow[NW];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    const int n = min(n0 + r, p.N - 1);  // rows past N are clamped (and not stored)
-    wrow[r] = n;
-    if (GLU) wrow[ROWS + r] = n + p.N;
-  }
-  float acc[MM][NW];
-#pragma unroll
-  for (int m = 0; m < MM; ++m)
-#pragma unroll
-    for (int r = 0; r < NW; ++r) acc[m][r] = 0.f;
+#include "gemv_mx_body.h"
+}
 
-  const int KB = p.K >> 5;  // blocks per row; lanes past it do nothing
-  for (int kb = lane; kb < KB; kb += 64) {
-    u32x4_t wv[NW];
-    float sc[NW];
-#pragma unroll
-    for (int r = 0; r < NW; ++r) {
-      wv[r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p.w + (int64_t)wrow[r] * p.ldw + (int64_t)kb * 16));
-      sc[r] = e8m0(p.scale[(int64_t)wrow[r] * p.lds + kb]);
-    }
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      W8 wb[NW];
-#pragma unroll
-      for (int r = 0; r < NW; ++r) wb[r] = cvt8(wv[r][d], sc[r]);
-#pragma unroll
-      for (int m = 0; m < MM; ++m) {
-        if (m < p.M) {
-          const u32x4_t xv = *reinterpret_cast<const u32x4_t*>(p.x + (int64_t)m * p.ldx + (int64_t)kb * 32 + d * 8);
-#pragma unroll
-          for (int r = 0; r < NW; ++r) acc[m][r] = dot8(xv, wb[r], acc[m][r]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int m = 0; m < MM; ++m)
-#pragma unroll
-    for (int r = 0; r < NW; ++r) acc[m][r] = wave_sum(acc[m][r]);
-  if (lane != 0) return;
-#pragma unroll
-  for (int m = 0; m < MM; ++m) {
-    if (m >= p.M) continue;
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      const int n = n0 + r;
-      if (n >= p.N) continue;
-      float v = acc[m][r];
-      if (p.bias) v += bf2f(p.bias[wrow[r]]);
-      if (GLU) {
-        float u = acc[m][ROWS + r];
-        if (p.bias) u += bf2f(p.bias[wrow[ROWS + r]]);
-        v = v / (1.f + __expf(-v)) * u;
-      }
-      p.y[(int64_t)m * p.ldy + n] = f2bf(v);
-    }
-  }
+// MoE experts: one product per blockIdx.y = pair, against expert e of a stack of E (codes w_estride
+// bytes apart, scales s_estride bytes apart).  e = eidx[pair] (selective: P (token, expert-slot)
+// pairs, M = 1, only the named experts' bytes are read) or e = pair (all experts, M <= 8 rows, each
+// expert's bytes read once).  x rows of pair start at (pair / xdiv) * x_pair_stride elements, its y
+// rows at pair * y_pair_stride.  An index outside [0, E) is clamped into the stack, never followed.
+struct ExpertParams {
+  Params g;              // pair 0 / expert 0 bases; bias is null
+  const int32_t* eidx;   // [pairs] on the device, or null: expert = pair
+  int64_t w_estride, s_estride;
+  int64_t x_pair_stride, y_pair_stride;
+  int E, xdiv;
+};
+static_assert(std::is_trivially_copyable<ExpertParams>::value && sizeof(ExpertParams) <= 4096, "kernel-argument struct");
+
+template <int MM, int ROWS, bool GLU>
+__global__ void __launch_bounds__(256) mx_expert_gemv_kernel(ExpertParams q) {
+  const int pair = blockIdx.y;
+  const int64_t e = q.eidx ? (int64_t)min(max(q.eidx[pair], 0), q.E - 1) : (int64_t)pair;
+  Params p = q.g;
+  p.w += e * q.w_estride;
+  p.scale += e * q.s_estride;
+  p.x += (int64_t)(pair / q.xdiv) * q.x_pair_stride;
+  p.y += (int64_t)pair * q.y_pair_stride;
+#include "gemv_mx_body.h"
 }
 
 // out_bf16[n, 32 kb .. 32 kb + 31] = deq(block kb of row n): one thread per 16-byte load
@@ -173,6 +136,29 @@ static int launch_t(const Params& p, hipStream_t s) {
   return 2;
 }
 
+template <int MM, bool GLU>
+static int launch_expert_m(const ExpertParams& q, int pairs, hipStream_t s) {
+  const int rows = rows_per_wave(q.g.N, q.g.K);
+  const int waves = (q.g.N + rows - 1) / rows;
+  dim3 grid((waves + 3) / 4, pairs), block(256);
+  if (rows == 4)
+    hipLaunchKernelGGL((mx_expert_gemv_kernel<MM, 4, GLU>), grid, block, 0, s, q);
+  else if (rows == 2)
+    hipLaunchKernelGGL((mx_expert_gemv_kernel<MM, 2, GLU>), grid, block, 0, s, q);
+  else
+    hipLaunchKernelGGL((mx_expert_gemv_kernel<MM, 1, GLU>), grid, block, 0, s, q);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+template <bool GLU>
+static int launch_expert_t(const ExpertParams& q, int pairs, hipStream_t s) {
+  if (q.g.M <= 1) return launch_expert_m<1, GLU>(q, pairs, s);
+  if (q.g.M <= 2) return launch_expert_m<2, GLU>(q, pairs, s);
+  if (q.g.M <= 4) return launch_expert_m<4, GLU>(q, pairs, s);
+  if (q.g.M <= 8) return launch_expert_m<8, GLU>(q, pairs, s);
+  return 2;
+}
+
 }  // namespace gemv_mx
 
 int mx_gemv_rows_per_wave(int N, int K) { return gemv_mx::rows_per_wave(N, K); }
@@ -184,6 +170,19 @@ int mx_gemv_launch(const void* x, int64_t ldx, const void* w, int64_t ldw, const
                     reinterpret_cast<const uint8_t*>(scale), lds, reinterpret_cast<const uint16_t*>(bias),
                     reinterpret_cast<uint16_t*>(y), ldy, M, N, K};
   return glu ? gemv_mx::launch_t<true>(p, stream) : gemv_mx::launch_t<false>(p, stream);
+}
+
+// MoE forms (see ExpertParams).  Selective: eidx [pairs] int32 on the device, M = 1.  All experts:
+// eidx null, pairs = E, M <= 8 rows per expert, x shared (x_pair_stride 0) or per expert.
+int mx_expert_gemv_launch(const void* x, int64_t ldx, int64_t x_pair_stride, const void* w, int64_t ldw, int64_t w_estride,
+                          const void* scale, int64_t lds, int64_t s_estride, const int32_t* eidx, int E, int pairs, int xdiv,
+                          void* y, int64_t ldy, int64_t y_pair_stride, int M, int N, int K, int glu, hipStream_t stream) {
+  if (M < 1 || N < 1 || K < 32 || (K & 31) || E < 1 || pairs < 1 || pairs > 65535 || xdiv < 1) return 2;
+  if (!eidx && pairs > E) return 2;
+  gemv_mx::ExpertParams q{{reinterpret_cast<const uint16_t*>(x), ldx, reinterpret_cast<const uint8_t*>(w), ldw,
+                           reinterpret_cast<const uint8_t*>(scale), lds, nullptr, reinterpret_cast<uint16_t*>(y), ldy, M, N, K},
+                          eidx, w_estride, s_estride, x_pair_stride, y_pair_stride, E, xdiv};
+  return glu ? gemv_mx::launch_expert_t<true>(q, pairs, stream) : gemv_mx::launch_expert_t<false>(q, pairs, stream);
 }
 
 int mx_dequant_launch(const void* w, int64_t ldw, const void* scale, int64_t lds, void* out, int N, int K,

@@ -17,6 +17,12 @@ the down projection, like a dense MLP):
 
 To feed the skinny-GEMM kernel, the expert weights are stored output-major ([E, out, in] in
 memory) while keeping their logical [E, in, out] parameter shapes (`post_load`).
+
+With MXFP4 experts (quantization_type="mxfp4": packed codes [E, out, in/2] + block scales, output-major
+as stored) the first two regimes read the 4-bit codes directly -- the selective and the all-experts
+(at most 8 tokens) kernels of csrc/gemv_mx.hip -- and anything larger dequantises the layer's
+experts into one bf16 scratch pair shared by all layers (E * 3 * H * I/tp * 2 bytes, allocated with
+the KV cache, before any graph capture) and runs the float code on it.
 DBRX differences handled here: LayerNorm without bias instead of RMSNorm (`norm_type`), QKV
 clamped to +-clip_qkv, optional top-k renormalisation (models/mixtral/convert.py translates its
 config and weights).
@@ -31,13 +37,15 @@ import torch.nn.functional as F
 
 from ..models.mixtral.modeling_mixtral import MixtralForCausalLM
 from ..ops._ext import ext, use_native
-from ..ops.gemv import expert_linear
+from ..ops.gemv import dequantize_mxfp4_into, expert_linear, mx_expert_linear, mx_experts_linear
 from ..ops.grouped_gemm import moe_dispatch, moe_permutation, moe_unpermute_combine
 from ..ops import swiglu
 from .model_base import DecoderInferenceMixin
 
 # below this many tokens a capture-safe dense all-experts dispatch is used outside selective loading
 _DENSE_MAX_TOKENS = 64
+# MXFP4 experts: the all-experts kernel carries at most this many rows per weight load (csrc/gemv_mx.hip)
+_MX_ALL_EXPERTS_MAX_TOKENS = 8
 
 
 class MoEInferenceModel(DecoderInferenceMixin, MixtralForCausalLM):
@@ -57,16 +65,42 @@ class MoEInferenceModel(DecoderInferenceMixin, MixtralForCausalLM):
 
     # ------------------------------------------------------------------ weights
     def _expert_weights(self, layer):
+        """Float experts: the logical weights [E, H, 2I/tp], [E, I/tp, H].  MXFP4 experts
+        (quantization_layers.MXFP4ExpertFused*): the (packed, scale) pairs of gate_up and down,
+        stored output-major ([E, 2I/tp, H/2] and [E, H, I/tp/2] codes)."""
         mo = layer.block_sparse_moe.expert_mlps.mlp_op
-        return mo.gate_up_proj.weight, mo.down_proj.weight   # [E, H, 2I/tp], [E, I/tp, H]
+        if mo.gate_up_proj.weight.dtype == torch.uint8:
+            return (mo.gate_up_proj.weight, mo.gate_up_proj.scale), (mo.down_proj.weight, mo.down_proj.scale)
+        return mo.gate_up_proj.weight, mo.down_proj.weight
+
+    def _experts_packed(self) -> bool:
+        return self.model.layers[0].block_sparse_moe.expert_mlps.mlp_op.gate_up_proj.weight.dtype == torch.uint8
 
     @torch.no_grad()
     def post_load(self) -> None:
-        """Re-lay the expert weights output-major in memory (logical shapes unchanged)."""
+        """Re-lay the float expert weights output-major in memory (logical shapes unchanged); MXFP4
+        experts are stored that way already."""
+        if self._experts_packed():
+            return
         for layer in self.model.layers:
             for w in self._expert_weights(layer):
                 if w.stride(-1) == 1 and w.shape[-1] > 1:
                     w.data = w.data.transpose(1, 2).contiguous().transpose(1, 2)
+
+    def setup_kv_cache(self, max_batch: int, max_len: int, device=None) -> torch.Tensor:
+        """With MXFP4 experts this is also where the prefill scratch is allocated: one output-major
+        pair ([E, 2I/tp, H], [E, H, I/tp], activation dtype: E * 3 * H * I/tp elements) shared by
+        all layers, which `_ffn` dequantises a layer's experts into.  It exists before any graph
+        is captured, so a captured prefill or large-batch step allocates nothing."""
+        kv = DecoderInferenceMixin.setup_kv_cache(self, max_batch, max_len, device)
+        if self._experts_packed():
+            (p_gu, _), (p_d, _) = self._expert_weights(self.model.layers[0])
+            shapes = [tuple(p.shape[:2]) + (p.shape[2] * 2,) for p in (p_gu, p_d)]
+            old = getattr(self, "_expert_scratch", None)
+            if old is None or old[0].device != kv.device or [tuple(t.shape) for t in old] != shapes:
+                dtype = self.model.embed_tokens.weight.dtype
+                self._expert_scratch = tuple(torch.empty(s, dtype=dtype, device=kv.device) for s in shapes)
+        return kv
 
     # ------------------------------------------------------------------ block pieces
     def _qkv_hook(self, qkv: torch.Tensor) -> torch.Tensor:
@@ -93,16 +127,24 @@ class MoEInferenceModel(DecoderInferenceMixin, MixtralForCausalLM):
     def _ffn(self, layer, h: torch.Tensor) -> torch.Tensor:
         shape = h.shape
         x = h.reshape(-1, shape[-1])
-        n, k, E = x.shape[0], self.top_k, self.num_experts
         top_w, top_i = self._route(layer, x)
-        w_gu, w_d = self._expert_weights(layer)
-        if n * k <= E:
-            out = self._selective(x, top_w, top_i, w_gu, w_d)
-        elif n <= _DENSE_MAX_TOKENS or (x.is_cuda and torch.cuda.is_current_stream_capturing()):
-            out = self._all_experts(x, top_w, top_i, w_gu, w_d)
-        else:
-            out = self._grouped(x, top_w, top_i, w_gu, w_d)
+        out = self._experts(x, top_w, top_i, *self._expert_weights(layer))
         return self._all_reduce(out).view(shape)
+
+    def _experts(self, x, top_w, top_i, w_gu, w_d):
+        """The dispatch of the module docstring on routed tokens x [n, H]; TP-partial result [n, H]."""
+        n, k, E = x.shape[0], self.top_k, self.num_experts
+        if isinstance(w_gu, tuple):   # MXFP4 experts: (packed, scale) pairs
+            if n * k <= E:
+                return self._selective_mx(x, top_w, top_i, w_gu, w_d)
+            if n <= _MX_ALL_EXPERTS_MAX_TOKENS:
+                return self._all_experts_mx(x, top_w, top_i, w_gu, w_d)
+            w_gu, w_d = self._dequantized_experts(w_gu, w_d)
+        if n * k <= E:
+            return self._selective(x, top_w, top_i, w_gu, w_d)
+        if n <= _DENSE_MAX_TOKENS or (x.is_cuda and torch.cuda.is_current_stream_capturing()):
+            return self._all_experts(x, top_w, top_i, w_gu, w_d)
+        return self._grouped(x, top_w, top_i, w_gu, w_d)
 
     def _selective(self, x, top_w, top_i, w_gu, w_d):
         n, k = top_i.shape
@@ -111,12 +153,37 @@ class MoEInferenceModel(DecoderInferenceMixin, MixtralForCausalLM):
         y = expert_linear(a, w_d.transpose(1, 2), eidx, xdiv=1)             # [n*k, H] partial over TP
         return (y.view(n, k, -1).float() * top_w.unsqueeze(-1)).sum(1).to(x.dtype)
 
+    def _selective_mx(self, x, top_w, top_i, gu, d):
+        """`_selective` on the 4-bit codes: only the chosen experts' codes and scales are read."""
+        n, k = top_i.shape
+        eidx = top_i.reshape(-1).to(torch.int32)
+        a = mx_expert_linear(x, gu[0], gu[1], eidx, xdiv=k, glu=True)       # [n*k, I/tp]
+        y = mx_expert_linear(a, d[0], d[1], eidx, xdiv=1)                   # [n*k, H] partial over TP
+        return (y.view(n, k, -1).float() * top_w.unsqueeze(-1)).sum(1).to(x.dtype)
+
     def _all_experts(self, x, top_w, top_i, w_gu, w_d):
         E = self.num_experts
         gu = torch.matmul(x.unsqueeze(0), w_gu)                              # [E, n, 2I/tp]
         y = torch.matmul(swiglu(gu), w_d)                                    # [E, n, H]
         dense_w = torch.zeros(x.shape[0], E, dtype=torch.float32, device=x.device).scatter_(1, top_i, top_w)
         return torch.einsum("enh,ne->nh", y.float(), dense_w).to(x.dtype)
+
+    def _all_experts_mx(self, x, top_w, top_i, gu, d):
+        """`_all_experts` for at most 8 tokens on the 4-bit codes, each expert's bytes read once."""
+        E = self.num_experts
+        a = mx_experts_linear(x, gu[0], gu[1], glu=True)                     # [E, n, I/tp]
+        y = mx_experts_linear(a, d[0], d[1])                                 # [E, n, H]
+        dense_w = torch.zeros(x.shape[0], E, dtype=torch.float32, device=x.device).scatter_(1, top_i, top_w)
+        return torch.einsum("enh,ne->nh", y.float(), dense_w).to(x.dtype)
+
+    def _dequantized_experts(self, gu, d):
+        """Prefill-sized inputs: this layer's experts dequantised into the scratch pair shared by all
+        layers (`setup_kv_cache`), returned in the logical [E, in, out] shapes over output-major
+        storage -- what `post_load` gives float experts, so `_all_experts` / `_grouped` run unchanged."""
+        s_gu, s_d = self._expert_scratch
+        dequantize_mxfp4_into(gu[0], gu[1], s_gu)
+        dequantize_mxfp4_into(d[0], d[1], s_d)
+        return s_gu.transpose(1, 2), s_d.transpose(1, 2)
 
     def _grouped(self, x, top_w, top_i, w_gu, w_d):
         """Prefill: (token, choice) slots sorted by expert on the device, each expert multiplying only

@@ -14,7 +14,11 @@ from __future__ import annotations
 import json
 import os
 
+import torch
+
 from ..models.mixtral.convert import dbrx_hf_to_nxd, dbrx_to_mixtral_config, mixtral_hf_to_nxd
+from ..parallel_layers import parallel_state as ps
+from ..parallel_layers.sharding import shard_state_dict
 from .config import InferenceConfig
 from .generation import LlamaForCausalLMInference
 from .modeling_moe import MoEInferenceModel
@@ -42,7 +46,38 @@ class _MoEInferenceBase(LlamaForCausalLMInference):
         return moe_config_from_dir(path)
 
     def _quantize(self) -> None:
-        raise NotImplementedError("weight-only quantization (int8, MXFP4) is implemented for dense decoders only")
+        """quantization_type="mxfp4": o_proj, the lm_head and the expert linears become MXFP4 weight-only
+        layers (quantization_layers.MXFP4*); the router and the fused QKV stay in the activation dtype."""
+        from ..quantization import convert, get_default_mxfp4_qconfig_dict, get_mxfp4_moe_quant_module_mappings
+
+        qt = str(self.config.quantization_type)
+        if qt != "mxfp4":
+            raise NotImplementedError(f"quantization_type={qt!r}: the MoE applications implement MXFP4 weight-only "
+                                      "quantization only; int8 MoE experts are not implemented for inference")
+        convert(self.model, get_default_mxfp4_qconfig_dict(), inplace=True, mapping=get_mxfp4_moe_quant_module_mappings())
+
+    def _load_full(self, full_sd) -> None:
+        """The packed expert parameters are output-major ([E, out, in/2]) while a full float expert
+        weight is [E, in, out], and shard_state_dict slices the full tensor by the parameter's
+        partition dim: give it the float expert weights output-major, and hand the layers the shard
+        back in its logical [E, in_local, out_local] shape (they quantize it on load)."""
+        keys = [n for n, p in self.model.named_parameters()
+                if p.dtype == torch.uint8 and p.dim() == 3 and n.endswith(".weight")
+                and n in full_sd and full_sd[n].is_floating_point()]
+        if not keys:
+            return super()._load_full(full_sd)
+        full_sd = dict(full_sd)
+        if self._mha_from is not None:
+            from ..modules.gqa import convert_state_dict_to_mha
+
+            full_sd = convert_state_dict_to_mha(full_sd, *self._mha_from)
+        for n in keys:
+            full_sd[n] = full_sd[n].transpose(1, 2)
+        tp, rank = ps.get_tensor_model_parallel_size(), ps.get_tensor_model_parallel_rank()
+        local = shard_state_dict(self.model, full_sd, tp, rank, strict=False)
+        for n in keys:
+            local[n] = local[n].transpose(1, 2)
+        self._load_local(local)
 
 
 class MixtralForCausalLMInference(_MoEInferenceBase):

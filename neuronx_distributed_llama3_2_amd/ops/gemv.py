@@ -169,11 +169,35 @@ def dequantize_mxfp4(packed: torch.Tensor, scale: torch.Tensor, dtype=torch.bflo
     """MXFP4 (packed [out, in/2], scale [out, in/32]) -> dtype [out, in].  On the GPU the bf16 result
     comes from the mx_dequant kernel (bit-identical to the torch form here)."""
     _check_mxfp4(packed, scale)
-    if use_native(packed, scale) and dtype == torch.bfloat16 and _mx_native_ok(packed, scale):
-        out = torch.empty((packed.shape[0], packed.shape[1] * 2), dtype=torch.bfloat16, device=packed.device)
-        ext().mx_dequant(packed, scale, out)
-        return out
+    if use_native(packed, scale) and dtype == torch.bfloat16:
+        if _mx_native_ok(packed, scale):
+            out = torch.empty((packed.shape[0], packed.shape[1] * 2), dtype=torch.bfloat16, device=packed.device)
+            ext().mx_dequant(packed, scale, out)
+            return out
+        if packed.dim() == 3 and packed.is_contiguous() and scale.is_contiguous() and packed.numel() > 0 and \
+                packed.data_ptr() % 16 == 0:
+            # an expert stack [E, out, in/2] is the 2-D kernel over its [E * out, in/2] view
+            E, Nw, K2 = packed.shape
+            out = torch.empty((E, Nw, K2 * 2), dtype=torch.bfloat16, device=packed.device)
+            ext().mx_dequant(packed.view(E * Nw, K2), scale.view(E * Nw, -1), out.view(E * Nw, K2 * 2))
+            return out
     return _dequantize_mxfp4_torch(packed, scale, dtype)
+
+
+def dequantize_mxfp4_into(packed: torch.Tensor, scale: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """dequantize_mxfp4 of a contiguous expert stack into a preallocated contiguous `out`
+    [E, out, in] (the MoE prefill scratch): no allocation, so it is safe under graph capture."""
+    _check_mxfp4(packed, scale)
+    if tuple(out.shape) != tuple(packed.shape[:-1]) + (packed.shape[-1] * 2,) or not out.is_contiguous():
+        raise ValueError(f"dequantize_mxfp4_into: out {tuple(out.shape)} against packed {tuple(packed.shape)}")
+    if use_native(packed, scale, out) and out.dtype == torch.bfloat16 and packed.is_contiguous() and \
+            scale.is_contiguous() and packed.numel() > 0 and packed.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0 \
+            and packed.shape[-1] % 16 == 0:
+        K2 = packed.shape[-1]
+        ext().mx_dequant(packed.view(-1, K2), scale.view(-1, scale.shape[-1]), out.view(-1, K2 * 2))
+    else:
+        out.copy_(_dequantize_mxfp4_torch(packed, scale, out.dtype))
+    return out
 
 
 def mx_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
@@ -204,3 +228,82 @@ def mx_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, bias: 
 
         y = swiglu(y)
     return y
+
+
+def _check_mx_stack(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, glu: bool, op: str) -> None:
+    _check_mxfp4(packed, scale)
+    if packed.dim() != 3 or packed.shape[2] * 2 != x.shape[-1]:
+        raise ValueError(f"{op}: x [..., {x.shape[-1]}] against a packed expert stack {tuple(packed.shape)}; "
+                         "expected [E, out, in/2]")
+    if glu and packed.shape[1] % 2:
+        raise ValueError(f"{op}: glu needs [gate; up] rows, got {packed.shape[1]} weight rows")
+
+
+def _mx_stack_native_ok(packed: torch.Tensor, scale: torch.Tensor) -> bool:
+    return packed.stride(2) == 1 and scale.stride(2) == 1 and packed.stride(1) % 16 == 0 and \
+        packed.stride(0) % 16 == 0 and packed.data_ptr() % 16 == 0 and packed.numel() > 0 and \
+        packed.stride(1) >= packed.shape[2] and scale.stride(1) >= scale.shape[2]
+
+
+def _glu(y: torch.Tensor) -> torch.Tensor:
+    from .activations import swiglu
+
+    return swiglu(y)
+
+
+def mx_expert_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, eidx: torch.Tensor, xdiv: int = 1,
+                     glu: bool = False) -> torch.Tensor:
+    """`expert_linear` on an MXFP4 expert stack (packed [E, Nw, K/2], scale [E, Nw, K/32], output-major):
+    y[p] = x[p // xdiv] @ deq(W[eidx[p]])^T for P (token, expert-slot) pairs; glu=True: rows
+    [gate; up] -> silu(gate) * up.  bf16 inputs on the GPU read only the selected experts' codes and
+    scales (csrc/gemv_mx.hip expert kernel; eidx stays on the device, static shapes, capturable);
+    everything else dequantises the selected experts and does a bmm."""
+    _check_mx_stack(x, packed, scale, glu, "mx_expert_linear")
+    if eidx.is_floating_point() or eidx.dtype == torch.bool:
+        raise TypeError(f"mx_expert_linear: eidx must be an integer tensor, got {eidx.dtype}")
+    xdiv = int(xdiv)
+    if xdiv < 1:
+        raise ValueError("mx_expert_linear: xdiv must be at least 1")
+    P = eidx.numel()
+    K = x.shape[-1]
+    Nw = packed.shape[1]
+    N = Nw // 2 if glu else Nw
+    x2 = x.reshape(-1, K)
+    if (P + xdiv - 1) // xdiv > x2.shape[0]:
+        raise ValueError(f"mx_expert_linear: {P} pairs with xdiv {xdiv} need more than the {x2.shape[0]} rows of x")
+    if use_native(x, packed, scale, eidx) and x.dtype == torch.bfloat16 and 1 <= P <= 65535 and N >= 1 and \
+            _mx_stack_native_ok(packed, scale):
+        if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
+            x2 = x2.contiguous()
+        y = torch.empty((P, N), dtype=torch.bfloat16, device=x.device)
+        ext().mx_expert_gemv(x2, packed, scale, eidx.reshape(-1).to(torch.int32).contiguous(), xdiv, y, glu)
+        return y
+    sel = eidx.reshape(-1).long()
+    w = dequantize_mxfp4(packed.index_select(0, sel), scale.index_select(0, sel), x.dtype)   # [P, Nw, K]
+    rows = x2.index_select(0, torch.arange(P, device=x.device) // xdiv)
+    y = torch.bmm(rows.unsqueeze(1), w.transpose(1, 2)).squeeze(1)
+    return _glu(y) if glu else y
+
+
+def mx_experts_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, glu: bool = False) -> torch.Tensor:
+    """Every expert of an MXFP4 stack on a few rows: y[e, m] = x[(e,) m] @ deq(W[e])^T with x shared
+    [M, K] or per expert [E, M, K]; result [E, M, N].  bf16 inputs with M <= 8 on the GPU read each
+    expert's 4-bit weights once (csrc/gemv_mx.hip expert kernel); everything else dequantises the
+    stack and does a bmm."""
+    _check_mx_stack(x, packed, scale, glu, "mx_experts_linear")
+    E, Nw = packed.shape[0], packed.shape[1]
+    if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[0] != E):
+        raise ValueError(f"mx_experts_linear: x must be [M, K] or [{E}, M, K], got {tuple(x.shape)}")
+    M, K = x.shape[-2], x.shape[-1]
+    N = Nw // 2 if glu else Nw
+    if use_native(x, packed, scale) and x.dtype == torch.bfloat16 and 1 <= M <= 8 and 1 <= E <= 65535 and N >= 1 and \
+            _mx_stack_native_ok(packed, scale):
+        if x.stride(-1) != 1 or x.stride(-2) % 8 or x.data_ptr() % 16 or (x.dim() == 3 and x.stride(0) % 8):
+            x = x.contiguous()
+        y = torch.empty((E, M, N), dtype=torch.bfloat16, device=x.device)
+        ext().mx_experts_gemv(x, packed, scale, y, glu)
+        return y
+    w = dequantize_mxfp4(packed, scale, x.dtype)                                             # [E, Nw, K]
+    xe = x.unsqueeze(0).expand(E, M, K) if x.dim() == 2 else x
+    y = torch.bmm(xe, w.transpose(1, 2))
+    return _glu(y) if glu else y

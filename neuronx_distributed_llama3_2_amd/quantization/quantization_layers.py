@@ -10,6 +10,8 @@ Same collectives as the float layers (TP all-reduce / SP reduce-scatter / gather
 
 MXFP4ColumnParallel / MXFP4RowParallel are the same pair with MXFP4 storage (packed 4-bit e2m1 codes and
 one E8M0 scale per 32 in-features, both uint8; format in ops/gemv.py, kernels in csrc/gemv_mx.hip).
+MXFP4ExpertFusedColumnParallel / MXFP4ExpertFusedRowParallel hold an MoE expert stack the same way,
+output-major ([E, out, in/2] codes), for the expert kernels of the same file.
 """
 
 from __future__ import annotations
@@ -21,7 +23,7 @@ from torch import nn
 from torch.nn.parameter import Parameter
 
 from ..modules.moe.moe_parallel_layers import ExpertFusedColumnParallelLinear, ExpertFusedRowParallelLinear
-from ..ops.gemv import MX_BLOCK, dequantize_weight, mx_linear, quantize_mxfp4, skinny_linear
+from ..ops.gemv import MX_BLOCK, dequantize_weight, mx_experts_linear, mx_linear, quantize_mxfp4, skinny_linear
 from ..parallel_layers import mappings
 from ..parallel_layers import parallel_state as ps
 from ..parallel_layers import sp
@@ -370,8 +372,119 @@ class MXFP4RowParallel(_MXFP4ParallelLinear):
         return new
 
 
+class _MXFP4ExpertFused(nn.Module):
+    """MXFP4 storage of an expert-fused linear (logical weight [E, in, out]): `weight` is the packed
+    uint8 [E, out_local, in_local/2] parameter, `scale` the E8M0 uint8 [E, out_local, in_local/32] one
+    -- output-major, which is what the expert kernels of csrc/gemv_mx.hip read.  Both keep the float
+    layer's TP sharding (column: out with the layer's stride, i.e. 2 for [gate; up]; row: in) on
+    the transposed axes, so a full float weight has to be output-major when it is sliced by these
+    parameters' partition dims (inference/moe.py `_load_full`)."""
+
+    def _setup_mx(self, num_experts: int, in_local: int, out_local: int, partition_dim: int, stride: int, dtype,
+                  device) -> None:
+        if in_local % MX_BLOCK != 0:
+            raise ValueError(f"MXFP4 needs the local in-features ({in_local}) to be a multiple of {MX_BLOCK}")
+        ep = ps.get_expert_model_parallel_size() if ps.model_parallel_is_initialized() else 1
+        self.num_experts = num_experts
+        self._n_local_experts = divide(num_experts, ep)
+        self.quantization_type = QuantizationType.MX_BLOCK
+        self.quantized_dtype = QuantizedDtype.MXFP4.value
+        self.dtype = dtype
+        E = self._n_local_experts
+        self.weight = Parameter(torch.zeros((E, out_local, in_local // 2), dtype=torch.uint8, device=device),
+                                requires_grad=False)
+        # e = 127 (scale 1) with zero codes: an unloaded layer dequantises to zeros
+        self.scale = Parameter(torch.full((E, out_local, in_local // MX_BLOCK), 127, dtype=torch.uint8, device=device),
+                               requires_grad=False)
+        for t in (self.weight, self.scale):
+            set_tensor_model_parallel_attributes(t, True, partition_dim, stride)
+            setattr(t, "expert_model_parallel", True)
+
+    def quantize_from(self, w_float: torch.Tensor) -> None:
+        """Quantise a float weight of this layer's logical (local) [E, in, out] shape."""
+        q, s = quantize_mxfp4(w_float.detach().transpose(1, 2).contiguous())
+        with torch.no_grad():
+            self.weight.copy_(q.to(self.weight.device))
+            self.scale.copy_(s.to(self.scale.device))
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                              error_msgs):
+        wk = prefix + "weight"
+        if wk in state_dict and state_dict[wk].is_floating_point():
+            w = state_dict[wk]
+            E, o, i2 = self.weight.shape
+            if tuple(w.shape) != (E, i2 * 2, o):
+                error_msgs.append(f"{wk}: a float expert weight must be [E, in, out] = {(E, i2 * 2, o)}, got {tuple(w.shape)}")
+                return
+            state_dict[wk], state_dict[prefix + "scale"] = quantize_mxfp4(w.transpose(1, 2).contiguous())
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                      error_msgs)
+
+    def _matmul(self, input_: torch.Tensor, expert_indices=None) -> torch.Tensor:
+        w, s = (self.weight, self.scale) if expert_indices is None else (self.weight[expert_indices], self.scale[expert_indices])
+        E = w.shape[0]
+        x = input_.to(self.dtype) if input_.dtype != self.dtype else input_
+        if x.shape[0] not in (1, E):
+            raise RuntimeError(f"input/weight expert count mismatch: {tuple(x.shape)} vs {E} experts")
+        x3 = x.reshape(x.shape[0], -1, x.shape[-1])
+        out = mx_experts_linear(x3[0] if x3.shape[0] == 1 and E > 1 else x3, w, s)
+        return out.view((E,) + tuple(x.shape[1:-1]) + (w.shape[1],))
+
+
+class MXFP4ExpertFusedColumnParallel(_MXFP4ExpertFused):
+    """[E, ..., H] -> [E, ..., out/tp] on MXFP4 expert weights."""
+
+    def __init__(self, num_experts: int, input_size: int, output_size: int, dtype: torch.dtype = torch.bfloat16,
+                 device: Optional[torch.device] = None, stride: int = 1, **kw):
+        super().__init__()
+        self.input_size, self.output_size, self.stride = input_size, output_size, stride
+        self._setup_mx(num_experts, input_size, divide(output_size, ps.get_tensor_model_parallel_size()), 1, stride, dtype,
+                       device)
+
+    def forward(self, input_: torch.Tensor, expert_indices: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self._matmul(input_, expert_indices)
+
+    @classmethod
+    def from_float(cls, mod: ExpertFusedColumnParallelLinear, q_config: BASE_QCONFIG_DICT_TYPE = None):
+        new = cls(mod.num_experts, mod.input_size, mod.output_size,
+                  dtype=mod.weight.dtype if mod.weight.is_floating_point() else torch.bfloat16,
+                  device=mod.weight.device, stride=mod.stride)
+        if mod.weight.device.type != "meta":
+            new.quantize_from(mod.weight)
+        return new
+
+
+class MXFP4ExpertFusedRowParallel(_MXFP4ExpertFused):
+    """[E, ..., in/tp] -> [E, ..., H] partial sums on MXFP4 expert weights (reduced over TP here when
+    `reduce_output` is set, as the float layer does)."""
+
+    def __init__(self, num_experts: int, input_size: int, output_size: int, reduce_output: bool = True,
+                 dtype: torch.dtype = torch.bfloat16, device: Optional[torch.device] = None, stride: int = 1, **kw):
+        super().__init__()
+        self.input_size, self.output_size, self.stride = input_size, output_size, stride
+        self.reduce_output = reduce_output
+        self._setup_mx(num_experts, divide(input_size, ps.get_tensor_model_parallel_size()), output_size, 2, stride, dtype,
+                       device)
+
+    def forward(self, input_: torch.Tensor, expert_indices: Optional[torch.Tensor] = None) -> torch.Tensor:
+        out = self._matmul(input_, expert_indices)
+        if self.reduce_output and ps.get_tensor_model_parallel_size() > 1:
+            out = mappings.reduce_from_tensor_model_parallel_region(out)
+        return out
+
+    @classmethod
+    def from_float(cls, mod: ExpertFusedRowParallelLinear, q_config: BASE_QCONFIG_DICT_TYPE = None):
+        new = cls(mod.num_experts, mod.input_size, mod.output_size, reduce_output=getattr(mod, "reduce_output", True),
+                  dtype=mod.weight.dtype if mod.weight.is_floating_point() else torch.bfloat16,
+                  device=mod.weight.device, stride=mod.stride)
+        if mod.weight.device.type != "meta":
+            new.quantize_from(mod.weight)
+        return new
+
+
 class MXFP4ExpertFusedUnsupported:
-    """The expert-fused MoE linears have no MXFP4 form."""
+    """Stub of the default MXFP4 mapping: convert() on a model with MoE experts refuses unless the
+    caller passes the mapping with the expert layers (get_mxfp4_moe_quant_module_mappings)."""
 
     @classmethod
     def from_float(cls, mod, q_config=None):
