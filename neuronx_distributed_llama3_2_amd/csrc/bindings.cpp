@@ -69,6 +69,8 @@ int mx_gemv_rows_per_wave(int, int);
 int mx_dequant_launch(const void*, int64_t, const void*, int64_t, void*, int, int, hipStream_t);
 int mx_expert_gemv_launch(const void*, int64_t, int64_t, const void*, int64_t, int64_t, const void*, int64_t, int64_t,
                           const int32_t*, int, int, int, void*, int64_t, int64_t, int, int, int, int, hipStream_t);
+int mx_mfma_launch(const void*, int64_t, int64_t, const void*, int64_t, int64_t, const void*, int64_t, int64_t, const void*,
+                   int, void*, int64_t, int64_t, int, int, int, int, int, hipStream_t);
 int expert_gemv_launch(const void*, int64_t, const void*, int64_t, int64_t, const int32_t*, int, int, void*, int64_t, int,
                        int, int, hipStream_t);
 void dgemv_set_knob(int, int);
@@ -996,6 +998,59 @@ void mx_experts_gemv(at::Tensor x, at::Tensor w, at::Tensor scale, at::Tensor y,
            "mx_experts_gemv");
 }
 
+// mx_gemv on MFMA weight tiles (csrc/gemv_mx_mfma.hip): the same operands and checks, 1 <= M <= 16.  cfg = 0 lets
+// the launcher pick tiles per wave / K split; the benchmark tools force them with cfg = 16 T + KS.
+void mx_gemm(at::Tensor x, at::Tensor w, at::Tensor scale, c10::optional<at::Tensor> bias, at::Tensor y, bool glu,
+             int64_t cfg) {
+  check_cuda(x, "x");
+  check_bf16(x, "x");
+  check_bf16(y, "y");
+  check_cuda(y, "y");
+  TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && x.stride(1) == 1 && y.stride(1) == 1, "mx_gemm: 2-D x / y, unit inner strides");
+  const int64_t M = x.size(0), K = x.size(1), N = y.size(1);
+  check_mx(w, scale, K, "mx_gemm");
+  TORCH_CHECK(M >= 1 && M <= 16 && y.size(0) == M, "mx_gemm: 1 <= M <= 16");
+  TORCH_CHECK(N >= 1 && w.size(0) == (glu ? 2 * N : N), "mx_gemm: weight shape mismatch");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && x.stride(0) >= K && y.stride(0) >= N &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "mx_gemm: 16-byte aligned activation rows required");
+  TORCH_CHECK(w.stride(0) >= K / 2 && scale.stride(0) >= K / 32, "mx_gemm: weight / scale rows must not overlap");
+  TORCH_CHECK(x.device() == w.device() && y.device() == w.device(), "mx_gemm: operands on different devices");
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    check_bf16(*bias, "bias");
+    check_cuda(*bias, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == w.size(0), "mx_gemm: bias must be [Nw]");
+    bp = bias->data_ptr();
+  }
+  check_rc(nxd::mx_mfma_launch(x.data_ptr(), x.stride(0), 0, w.data_ptr(), w.stride(0), 0, scale.data_ptr(), scale.stride(0), 0,
+                               bp, 1, y.data_ptr(), y.stride(0), 0, (int)M, (int)N, (int)K, glu, (int)cfg, cur_stream()),
+           "mx_gemm");
+}
+
+// mx_experts_gemv on MFMA weight tiles: every expert, 1 <= M <= 16 rows; x [M, K] (shared) or [E, M, K], y [E, M, N]
+void mx_experts_gemm(at::Tensor x, at::Tensor w, at::Tensor scale, at::Tensor y, bool glu, int64_t cfg) {
+  check_cuda(x, "x");
+  check_bf16(x, "x");
+  check_cuda(y, "y");
+  check_bf16(y, "y");
+  TORCH_CHECK((x.dim() == 2 || x.dim() == 3) && y.dim() == 3 && x.stride(-1) == 1 && y.stride(2) == 1,
+              "mx_experts_gemm: x [M, K] or [E, M, K], y [E, M, N], unit inner strides");
+  const int64_t E = y.size(0), M = y.size(1), N = y.size(2), K = x.size(-1);
+  check_mx_stack(w, scale, K, glu ? 2 * N : N, "mx_experts_gemm");
+  TORCH_CHECK(w.size(0) == E && E <= 65535, "mx_experts_gemm: y [E, M, N] against E experts");
+  TORCH_CHECK(M >= 1 && M <= 16 && x.size(-2) == M && (x.dim() == 2 || x.size(0) == E), "mx_experts_gemm: 1 <= M <= 16 rows");
+  const int64_t ldx = x.stride(-2), xps = x.dim() == 3 ? x.stride(0) : 0;
+  TORCH_CHECK(ldx % 8 == 0 && xps % 8 == 0 && ldx >= K && xps >= 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "mx_experts_gemm: 16-byte aligned activation rows required");
+  TORCH_CHECK(y.stride(1) >= N && y.stride(0) >= M * y.stride(1), "mx_experts_gemm: y rows must not overlap");
+  TORCH_CHECK(x.device() == w.device() && y.device() == w.device(), "mx_experts_gemm: operands on different devices");
+  check_rc(nxd::mx_mfma_launch(x.data_ptr(), ldx, xps, w.data_ptr(), w.stride(1), w.stride(0), scale.data_ptr(),
+                               scale.stride(1), scale.stride(0), nullptr, (int)E, y.data_ptr(), y.stride(1), y.stride(0),
+                               (int)M, (int)N, (int)K, glu, (int)cfg, cur_stream()),
+           "mx_experts_gemm");
+}
+
 void mx_dequant(at::Tensor w, at::Tensor scale, at::Tensor out) {
   check_bf16(out, "out");
   check_cuda(out, "out");
@@ -1341,6 +1396,10 @@ PYBIND11_MODULE(_C, m) {
   m.def("dequant_int8", &dequant_int8);
   m.def("expert_gemv", &expert_gemv);
   m.def("mx_gemv", &mx_gemv);
+  m.def("mx_gemm", &mx_gemm, py::arg("x"), py::arg("w"), py::arg("scale"), py::arg("bias"), py::arg("y"), py::arg("glu"),
+        py::arg("cfg") = 0);
+  m.def("mx_experts_gemm", &mx_experts_gemm, py::arg("x"), py::arg("w"), py::arg("scale"), py::arg("y"), py::arg("glu"),
+        py::arg("cfg") = 0);
   m.def("mx_dequant", &mx_dequant);
   m.def("mx_expert_gemv", &mx_expert_gemv);
   m.def("mx_experts_gemv", &mx_experts_gemv);

@@ -22,6 +22,7 @@ so code * 2^X is exact in bf16 over the normal range: dequantisation to bf16 los
 
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -200,12 +201,30 @@ def dequantize_mxfp4_into(packed: torch.Tensor, scale: torch.Tensor, out: torch.
     return out
 
 
+# NXD_MX_MFMA: the smallest row count M from which mx_linear takes the MFMA form of the MXFP4 decode product
+# (csrc/gemv_mx_mfma.hip, up to MX_GEMM_MAX_ROWS rows); 0 = never.  Rows 9..16 take it whenever it is
+# on, so values above 9 mean 9.  Read once per process.  Default 4: the smallest measured row count
+# from which the MFMA form beats the VALU kernel at every shape of tools/bench_mx_gemv.py (at 2 rows
+# it loses at three of the seven, profiles/mxfp4_mfma_gemv.jsonl).
+MX_GEMM_MAX_ROWS = 16
+_MX_MFMA_DEFAULT = 4
+_MX_MFMA = int(os.environ.get("NXD_MX_MFMA", str(_MX_MFMA_DEFAULT)))
+
+
+def mx_route(M: int) -> str:
+    """Which form an M-row MXFP4 product takes once the native path applies: "gemv" (VALU kernel,
+    M <= 8), "gemm" (MFMA weight tiles, M <= 16) or "dequant" (dequantise + GEMM)."""
+    if _MX_MFMA > 0 and min(_MX_MFMA, 9) <= M <= MX_GEMM_MAX_ROWS:
+        return "gemm"
+    return "gemv" if 1 <= M <= 8 else "dequant"
+
+
 def mx_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
               glu: bool = False) -> torch.Tensor:
     """x [..., K] @ deq(W)^T (+ bias) for MXFP4 W (packed [Nw, K/2], scale [Nw, K/32]); glu=True:
     W = [gate; up] rows and the result is silu(gate) * up of width Nw / 2.  Decode-sized bf16 inputs
-    on the GPU (M <= 8) read the 4-bit weights directly (mx_gemv); everything else dequantises and
-    goes through the GEMM."""
+    on the GPU (M <= 16) read the 4-bit weights directly (mx_gemv or mx_gemm, see mx_route);
+    everything else dequantises and goes through the GEMM."""
     _check_mxfp4(packed, scale)
     K = x.shape[-1]
     if packed.dim() != 2 or packed.shape[1] * 2 != K:
@@ -214,13 +233,15 @@ def mx_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, bias: 
     M = x.numel() // K
     Nw = packed.shape[0]
     N = Nw // 2 if glu else Nw
-    if use_native(x, packed, scale) and 1 <= M <= 8 and x.dtype == torch.bfloat16 and N >= 1 and \
+    route = mx_route(M)
+    if use_native(x, packed, scale) and route != "dequant" and x.dtype == torch.bfloat16 and N >= 1 and \
             _mx_native_ok(packed, scale) and (bias is None or bias.dtype == torch.bfloat16):
         x2 = x.reshape(M, K)
         if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
             x2 = x2.contiguous()
         y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-        ext().mx_gemv(x2, packed, scale, bias.contiguous() if bias is not None else None, y, glu)
+        kernel = ext().mx_gemm if route == "gemm" else ext().mx_gemv
+        kernel(x2, packed, scale, bias.contiguous() if bias is not None else None, y, glu)
         return y.view(lead + (N,))
     y = _linear(x, dequantize_mxfp4(packed, scale, x.dtype), bias)
     if glu:
@@ -289,7 +310,8 @@ def mx_experts_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor
     """Every expert of an MXFP4 stack on a few rows: y[e, m] = x[(e,) m] @ deq(W[e])^T with x shared
     [M, K] or per expert [E, M, K]; result [E, M, N].  bf16 inputs with M <= 8 on the GPU read each
     expert's 4-bit weights once (csrc/gemv_mx.hip expert kernel); everything else dequantises the
-    stack and does a bmm."""
+    stack and does a bmm.  (mx_route does not apply here: the MFMA expert form, ext().mx_experts_gemm,
+    is built and tested as a kernel but not routed to.)"""
     _check_mx_stack(x, packed, scale, glu, "mx_experts_linear")
     E, Nw = packed.shape[0], packed.shape[1]
     if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[0] != E):

@@ -1,5 +1,6 @@
 """MoE decode projection A/B on one MI355X: the MXFP4 expert kernels (mx_expert_linear /
-mx_experts_linear, csrc/gemv_mx.hip) against the bf16 forms (expert_linear, csrc/gemv.hip; the
+mx_experts_linear, csrc/gemv_mx.hip; the all-experts form at 8 and 16 rows also on the MFMA weight
+tiles of csrc/gemv_mx_mfma.hip) against the bf16 forms (expert_linear, csrc/gemv.hip; the
 all-experts matmuls of inference/modeling_moe.py) at the Mixtral-8x7B TP=1 expert shapes, and
 with --e2e the decode time per token of a Mixtral-shaped 4-layer random model, bf16 against MXFP4.
 
@@ -17,8 +18,8 @@ import time
 import torch
 
 sys.path.insert(0, ".")
-from neuronx_distributed_llama3_2_amd.ops import swiglu  # noqa: E402
-from neuronx_distributed_llama3_2_amd.ops.gemv import expert_linear, mx_expert_linear, mx_experts_linear  # noqa: E402
+from neuronx_distributed_llama3_2_amd.ops import ext, swiglu  # noqa: E402
+from neuronx_distributed_llama3_2_amd.ops.gemv import dequantize_mxfp4_into, expert_linear, mx_expert_linear  # noqa: E402
 
 E, H, I = 8, 4096, 14336   # Mixtral-8x7B
 OPS = [("gate_up", H, 2 * I, True), ("down", I, H, False)]   # op, K, weight rows, glu
@@ -26,7 +27,7 @@ ROTATE_BYTES = 512 << 20
 
 
 def expert_bytes(kind, Nw, K):
-    return Nw * K // 2 + Nw * K // 32 if kind == "mxfp4" else Nw * K * 2
+    return Nw * K // 2 + Nw * K // 32 if kind.startswith("mxfp4") else Nw * K * 2
 
 
 def make_stacks(kind, Nw, K):
@@ -41,10 +42,27 @@ def make_stacks(kind, Nw, K):
     return out
 
 
+_SCRATCH = {}
+
+
 def call(kind, form, x, w, eidx, glu):
     if form == "all":
-        if kind == "mxfp4":
-            return mx_experts_linear(x, w[0], w[1], glu=glu)
+        if kind.startswith("mxfp4"):
+            # both bodies called directly, whatever NXD_MX_MFMA routes to: the VALU kernel (at most 8
+            # rows; above, the route without an MFMA form: dequantise the stack into a scratch, then
+            # the bf16 matmul) and the MFMA weight tiles
+            M, N = x.shape[-2], w[0].shape[1] // (2 if glu else 1)
+            if kind == "mxfp4" and M > 8:
+                key = tuple(w[0].shape)
+                if key not in _SCRATCH:
+                    _SCRATCH[key] = torch.empty(w[0].shape[:2] + (w[0].shape[2] * 2,), dtype=torch.bfloat16, device="cuda")
+                s = _SCRATCH[key]
+                dequantize_mxfp4_into(w[0], w[1], s)
+                y = torch.matmul(x.unsqueeze(0) if x.dim() == 2 else x, s.transpose(1, 2))
+                return swiglu(y) if glu else y
+            y = torch.empty((E, M, N), dtype=torch.bfloat16, device="cuda")
+            (ext().mx_experts_gemv if kind == "mxfp4" else ext().mx_experts_gemm)(x, w[0], w[1], y, glu)
+            return y
         # the bf16 all-experts step of MoEInferenceModel._all_experts on output-major weights
         y = torch.matmul(x.unsqueeze(0) if x.dim() == 2 else x, w[0].transpose(1, 2))
         return swiglu(y) if glu else y
@@ -86,13 +104,18 @@ def emit(rec, sink):
 
 
 def bench_kernels(a, sink):
-    kinds = ("mxfp4", "bf16")
     for op, K, Nw, glu in OPS:
-        stacks = {k: make_stacks(k, Nw, K) for k in kinds}
+        stacks = {k: make_stacks(k, Nw, K) for k in ("mxfp4", "bf16")}
+        stacks["mxfp4_mfma"] = stacks["mxfp4"]
         # form, pairs / rows, expert choices to rotate over (2 pairs: four disjoint choices of two
-        # experts; 8 pairs: every expert once, the most bytes 8 pairs can read)
-        forms = [("selective", 2, [[0, 1], [2, 3], [4, 5], [6, 7]]), ("selective", 8, [list(range(8))]), ("all", 8, [None])]
+        # experts; 8 pairs: every expert once, the most bytes 8 pairs can read); the all-experts form
+        # at 8 and 16 rows with both MXFP4 bodies (see call)
+        forms = [("selective", 2, [[0, 1], [2, 3], [4, 5], [6, 7]]), ("selective", 8, [list(range(8))]), ("all", 8, [None]),
+                 ("all", 16, [None])]
         for form, P, choices in forms:
+            if a.forms and form not in a.forms.split(","):
+                continue
+            kinds = ("mxfp4", "mxfp4_mfma", "bf16") if form == "all" else ("mxfp4", "bf16")
             eidxs = [None if c is None else torch.tensor(c, dtype=torch.int32, device="cuda") for c in choices]
             if form == "all":
                 x = torch.randn(P, K, device="cuda", dtype=torch.bfloat16) if glu else \
@@ -116,14 +139,17 @@ def bench_kernels(a, sink):
                       "weights": k, "us": round(us, 2), "us_min": round(min(samples[k]), 2),
                       "us_max": round(max(samples[k]), 2), "weight_bytes": nbytes,
                       "weight_TBps": round(nbytes / us / 1e6, 3), "rounds": a.rounds, "stacks": len(stacks[k])}, sink)
-            spread = max((max(samples[k]) - min(samples[k])) / med[k] for k in kinds)
-            emit({"bench": "mx_expert_gemv", "op": op, "form": form, "pairs_or_rows": P, "compare": "mxfp4 / bf16",
-                  "time_ratio": round(med["mxfp4"] / med["bf16"], 3),
-                  "byte_ratio": round(expert_bytes("mxfp4", Nw, K) / expert_bytes("bf16", Nw, K), 3),
-                  "worst_relative_spread": round(spread, 3),
-                  "faster_by_more_than_spread": bool(max(samples["mxfp4"]) < min(samples["bf16"]))}, sink)
+            pairs = [("mxfp4", "bf16")] + ([("mxfp4_mfma", "bf16"), ("mxfp4_mfma", "mxfp4")] if form == "all" else [])
+            for n, d in pairs:
+                spread = max((max(samples[k]) - min(samples[k])) / med[k] for k in (n, d))
+                emit({"bench": "mx_expert_gemv", "op": op, "form": form, "pairs_or_rows": P, "compare": f"{n} / {d}",
+                      "time_ratio": round(med[n] / med[d], 3),
+                      "byte_ratio": round(expert_bytes(n, Nw, K) / expert_bytes(d, Nw, K), 3),
+                      "worst_relative_spread": round(spread, 3),
+                      "faster_by_more_than_spread": bool(max(samples[n]) < min(samples[d]))}, sink)
             del graphs
         del stacks
+        _SCRATCH.clear()
         torch.cuda.empty_cache()
 
 
@@ -189,6 +215,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--e2e", action="store_true", help="also time the Mixtral-shaped random model")
     ap.add_argument("--skip-kernels", action="store_true")
+    ap.add_argument("--forms", default=None, help="kernel forms to time: selective,all (default both)")
     ap.add_argument("--layers", type=int, default=4)
     ap.add_argument("--tokens", type=int, default=64)
     a = ap.parse_args()

@@ -1,8 +1,10 @@
-"""Decode projection A/B on one MI355X: mx_linear (MXFP4 weights, csrc/gemv_mx.hip) against
-skinny_linear with int8 and with bf16 weights (csrc/gemv.hip) on Llama-3.2-1B / Llama-3-8B
-projection shapes at 1, 4 and 8 activation rows.
+"""Decode projection A/B on one MI355X: MXFP4 weights on the VALU kernel (mx_gemv, csrc/gemv_mx.hip;
+above its 8 rows mx_dequant + GEMM, the route without an MFMA form) and on MFMA weight tiles
+(mx_gemm, csrc/gemv_mx_mfma.hip) against skinny_linear with int8 and with bf16 weights
+(csrc/gemv.hip) on Llama-3.2-1B / Llama-3-8B projection shapes at 1..16 activation rows.  The two
+MXFP4 kernels are called directly, so the result does not depend on the routing knob NXD_MX_MFMA.
 
-The three variants alternate in one process.  Each is a captured hipGraph of calls that rotate over
+The four variants alternate in one process.  Each is a captured hipGraph of calls that rotate over
 enough weight copies to exceed the 256 MiB Infinity Cache, so every call streams its weights from
 HBM.  One JSON line per (shape, rows, variant): median time per call, weight bytes per second and
 the run-to-run spread (min / max over the rounds)."""
@@ -14,7 +16,9 @@ import sys
 import torch
 
 sys.path.insert(0, ".")
-from neuronx_distributed_llama3_2_amd.ops.gemv import mx_linear, skinny_linear  # noqa: E402
+from neuronx_distributed_llama3_2_amd.ops import ext, swiglu  # noqa: E402
+from neuronx_distributed_llama3_2_amd.ops.gemm import linear  # noqa: E402
+from neuronx_distributed_llama3_2_amd.ops.gemv import dequantize_mxfp4, skinny_linear  # noqa: E402
 
 SHAPES = [  # model, op, K, weight rows, glu
     ("llama3.2-1b", "qkv", 2048, 3072, False),
@@ -29,14 +33,14 @@ ROTATE_BYTES = 512 << 20
 
 
 def weight_bytes(kind, Nw, K):
-    return {"mxfp4": Nw * K // 2 + Nw * K // 32, "int8": Nw * K + Nw * 4, "bf16": Nw * K * 2}[kind]
+    return {"mxfp4": Nw * K // 2 + Nw * K // 32, "int8": Nw * K + Nw * 4, "bf16": Nw * K * 2}[kind.split("_")[0]]
 
 
 def make_weights(kind, Nw, K, copies):
     dev = "cuda"
     ws = []
     for _ in range(copies):
-        if kind == "mxfp4":
+        if kind.startswith("mxfp4"):
             ws.append((torch.randint(0, 256, (Nw, K // 2), device=dev, dtype=torch.uint8),
                        torch.randint(120, 128, (Nw, K // 32), device=dev, dtype=torch.uint8)))
         elif kind == "int8":
@@ -47,9 +51,21 @@ def make_weights(kind, Nw, K, copies):
     return ws
 
 
+MFMA_CFG = 0   # --cfg: force tiles per wave / K split of mx_gemm (16 T + KS), 0 = the launcher's choice
+
+
 def call(kind, x, w, glu):
-    if kind == "mxfp4":
-        return mx_linear(x, w[0], w[1], glu=glu)
+    if kind.startswith("mxfp4"):
+        M, N = x.shape[0], w[0].shape[0] // (2 if glu else 1)
+        if kind == "mxfp4" and M > 8:   # no VALU form: dequantise the whole weight, then the GEMM
+            y = linear(x, dequantize_mxfp4(w[0], w[1], x.dtype), None)
+            return swiglu(y) if glu else y
+        y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+        if kind == "mxfp4":
+            ext().mx_gemv(x, w[0], w[1], None, y, glu)
+        else:
+            ext().mx_gemm(x, w[0], w[1], None, y, glu, MFMA_CFG)
+        return y
     return skinny_linear(x, w[0], w[1], glu=glu)
 
 
@@ -82,11 +98,17 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--rows", default="1,4,8")
     ap.add_argument("--only", default=None, help="model name filter")
+    ap.add_argument("--kinds", default="mxfp4,mxfp4_mfma,int8,bf16")
+    ap.add_argument("--cfg", type=int, default=0, help="force mx_gemm's tiles per wave T and K split KS: 16 T + KS")
     a = ap.parse_args()
+    global MFMA_CFG
+    MFMA_CFG = a.cfg
     if not torch.cuda.is_available():
         raise SystemExit("bench_mx_gemv needs a GPU")
     sink = open(a.out, "a") if a.out else None
-    kinds = ("mxfp4", "int8", "bf16")
+    kinds = tuple(a.kinds.split(","))
+    if any(not 1 <= int(m) <= 16 for m in a.rows.split(",")):
+        raise SystemExit("--rows: 1..16")
     for model, op, K, Nw, glu in SHAPES:
         if a.only and a.only != model:
             continue
@@ -111,6 +133,8 @@ def main():
                        "us": round(us, 2), "us_min": round(min(samples[k]), 2), "us_max": round(max(samples[k]), 2),
                        "weight_bytes": nbytes, "weight_TBps": round(nbytes / us / 1e6, 3), "rounds": a.rounds,
                        "copies": len(weights[k])}
+                if k == "mxfp4_mfma" and a.cfg:
+                    rec["cfg"] = a.cfg
                 line = json.dumps(rec)
                 print(line, flush=True)
                 if sink:
