@@ -2,6 +2,10 @@
 
 Runs only on an MI355X (marker `gpu`).  Each test also asserts that the native extension is the
 code path in use (no silent fallback).
+
+The flash-attention tests here are max-norm checks at large shapes; the edge shapes (mask
+boundaries, tile tails, GQA and item sums, the rescale paths, dropout masks) are held per element
+against an fp64 reference in tests/test_flash_attention_gpu.py.
 """
 
 import math
