@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "decode_attn.h"
 
 #include <execinfo.h>
 #include <csignal>
@@ -46,9 +47,6 @@ int clip_coef_launch(const float*, float*, float, int, hipStream_t);
 int scale_flat_launch(float*, int64_t, const float*, hipStream_t);
 int embedding_fwd_launch(const int64_t*, const void*, void*, int64_t, int, int64_t, int64_t, hipStream_t);
 int embedding_bwd_launch(const int64_t*, const void*, float*, int64_t, int, int64_t, int64_t, hipStream_t);
-int decode_attn_launch(const void*, const int64_t*, const void*, const void*, const int64_t*, const int*, const int*,
-                       float*, float*, float*, int*, void*, const int64_t*, int, int, int, int, int, int, float, hipStream_t,
-                       int, const void*, const void*, const int64_t*);
 int kv_cache_write_launch(const void*, const void*, const int64_t*, void*, void*, const int64_t*, const int*, const int*,
                           int, int, int, int, int, hipStream_t);
 int kv_write_mx8_launch(const void*, const void*, const int64_t*, void*, void*, void*, void*, const int*, const int*, int, int,
@@ -74,27 +72,17 @@ int mx_mfma_launch(const void*, int64_t, int64_t, const void*, int64_t, int64_t,
 int expert_gemv_launch(const void*, int64_t, const void*, int64_t, int64_t, const int32_t*, int, int, void*, int64_t, int,
                        int, int, hipStream_t);
 void dgemv_set_knob(int, int);
-void decode_attn_set_v2(int);
-void decode_attn_set_prefetch(const void*, int64_t, const void*, int64_t, int);
-void decode_attn_set_trace(uint64_t*);
 int dgemv_launch(int, const void*, int64_t, const void*, float, const void*, int64_t, void*, int64_t, int, int, int, int,
                  int, int, const float*, const float*, const int64_t*, int, void*, void*, int64_t, int64_t, int64_t,
                  const int*, int, int, const float*, float*, hipStream_t, const int64_t*, int64_t, void*, float*);
 int grouped_gemm_launch(int, const void*, const void*, void*, const int*, int, int, int, int, hipStream_t);
 int wgrad_gemm_launch(const void*, int64_t, const void*, int64_t, float*, int64_t, int, int, int, int, hipStream_t);
 int wgrad_gemm_choose_splits(int, int, int);
-int decode_attn_oproj_launch(const void*, const int64_t*, const void*, const void*, const int64_t*, const int*, const int*,
-                             const void*, int64_t, int, float*, float*, float*, float*, float*, int, int, int, int, int, int, float, hipStream_t,
-                             int);
 int grouped_rowgemm_launch(int, const void*, const void*, void*, const int*, int, int, int, int, hipStream_t);
 int wgrad_gemm_grouped_launch(const void*, int64_t, const void*, int64_t, float*, int64_t, int64_t, const int*, int, int,
                               int, int, hipStream_t);
 int dense_gemm_launch(int, int, const void*, int64_t, const void*, int64_t, void*, int64_t, int, int, int, int, hipStream_t);
 int dense_gemm_choose_splits(int, int, int);
-void decode_attn_set_oproj_maxl(int);
-int decode_attn_oproj_maxl();
-int decode_attn_sync_error(bool);
-void decode_attn_set_sync(int);
 int cu_stream_launch(const void*, void*, int64_t, int, int64_t, hipStream_t);
 int moe_combine_fwd_launch(const void*, const int64_t*, const float*, void*, int64_t, int, int, hipStream_t);
 int moe_combine_bwd_launch(const void*, const void*, const int64_t*, const float*, void*, float*, int64_t, int, int,
@@ -522,6 +510,39 @@ void decode_attn_prefetch(c10::optional<at::Tensor> a, int64_t a_bytes, c10::opt
   nxd::decode_attn_set_prefetch(ra.first, ra.second, rb.first, rb.second, (int)wgs);
 }
 
+// Cache row of each batch entry: an int32 cache_idx [B], or without one the identity over a cache of at
+// least B rows (null)
+const int* cache_rows(const c10::optional<at::Tensor>& cache_idx, const at::Tensor& kc, int64_t B) {
+  if (!cache_idx.has_value()) {
+    TORCH_CHECK(kc.size(0) >= B, "cache batch too small");
+    return nullptr;
+  }
+  TORCH_CHECK(cache_idx->scalar_type() == at::kInt && cache_idx->numel() == B, "cache_idx must be int32 [B]");
+  return cache_idx->data_ptr<int>();
+}
+
+// What decode_attn and decode_attn_oproj share of a call (csrc/decode_attn.h), checked: q with the strides
+// bshd_strides gave, the caches [Bc, Hkv, Lmax, D] (their format is the caller's to check), window,
+// seq_len and the cache rows.  Everything else stays zero / null for the caller to set.
+nxd::DecodeAttnArgs decode_attn_args(const at::Tensor& q, const int64_t* qs, const at::Tensor& kc, const at::Tensor& vc,
+                                     const c10::optional<at::Tensor>& cache_idx, const at::Tensor& seq_len, double scale,
+                                     int64_t window) {
+  nxd::DecodeAttnArgs a{};
+  a.B = q.size(0); a.T = q.size(1); a.Hq = q.size(2); a.D = q.size(3);
+  a.Hkv = kc.size(1); a.Lmax = kc.size(2);
+  TORCH_CHECK(window >= 0, "window must be >= 0 (0: none)");
+  TORCH_CHECK(seq_len.scalar_type() == at::kInt && seq_len.numel() == a.B && seq_len.is_contiguous(), "seq_len must be int32 [B]");
+  a.cache_idx = cache_rows(cache_idx, kc, a.B);
+  a.seq_len = seq_len.data_ptr<int>();
+  a.q = q.data_ptr(); a.q_sb = qs[0]; a.q_st = qs[1]; a.q_sh = qs[2];
+  a.kc = kc.data_ptr(); a.vc = vc.data_ptr();
+  a.c_sb = kc.stride(0); a.c_sh = kc.stride(1); a.c_sl = kc.stride(2);
+  a.scale = (float)scale;
+  a.window = window >= a.Lmax ? 0 : (int)window;   // covers the cache: no window
+  a.stream = cur_stream();
+  return a;
+}
+
 // Fused decode attention + o_proj (csrc/decode_attn.hip FUSE): oacc [B*T, Hout] fp32 (zero on entry)
 // += o_proj(attention).  Returns false (nothing launched) for shapes the fused kernel does not cover.
 bool decode_attn_oproj(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional<at::Tensor> cache_idx, at::Tensor seq_len,
@@ -533,40 +554,27 @@ bool decode_attn_oproj(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional
   check_bf16(wo, "wo");
   TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.sizes() == kc.sizes() && vc.is_contiguous(),
               "caches must be contiguous [B, Hkv, Lmax, D]");
-  const int B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
-  const int Hkv = kc.size(1), Lmax = kc.size(2);
-  TORCH_CHECK(kc.size(3) == D, "head dim mismatch");
-  TORCH_CHECK(window >= 0, "window must be >= 0 (0: none)");
-  TORCH_CHECK(wo.dim() == 2 && wo.stride(1) == 1 && wo.size(1) == (int64_t)Hq * D, "wo must be [Hout, Hq * D]");
+  TORCH_CHECK(kc.size(3) == q.size(3), "head dim mismatch");
+  TORCH_CHECK(wo.dim() == 2 && wo.stride(1) == 1 && wo.size(1) == q.size(2) * q.size(3), "wo must be [Hout, Hq * D]");
   check_aligned16(wo, "wo");
   const int64_t Hout = wo.size(0);
   TORCH_CHECK(oacc.scalar_type() == at::kFloat && oacc.is_cuda() && oacc.is_contiguous() && oacc.dim() == 2 &&
-                  oacc.size(0) >= (int64_t)B * T && oacc.size(1) == Hout,
+                  oacc.size(0) >= q.size(0) * q.size(1) && oacc.size(1) == Hout,
               "oacc must be fp32 contiguous [>= B*T, Hout]");
-  TORCH_CHECK(seq_len.scalar_type() == at::kInt && seq_len.numel() == B && seq_len.is_contiguous(), "seq_len must be int32 [B]");
-  const int* ci = nullptr;
-  if (cache_idx.has_value()) {
-    TORCH_CHECK(cache_idx->scalar_type() == at::kInt && cache_idx->numel() == B, "cache_idx must be int32 [B]");
-    ci = cache_idx->data_ptr<int>();
-  } else {
-    TORCH_CHECK(kc.size(0) >= B, "cache batch too small");
-  }
-  if (Hkv <= 0 || Hq % Hkv || Hout > INT32_MAX) return false;
-  const int64_t cs[3] = {kc.stride(0), kc.stride(1), kc.stride(2)};
+  nxd::DecodeAttnArgs a = decode_attn_args(q, qs, kc, vc, cache_idx, seq_len, scale, window);
+  if (a.Hkv <= 0 || a.Hq % a.Hkv || Hout > INT32_MAX) return false;
+  nxd::DecodeOprojArgs o{};
+  o.wo = wo.data_ptr(); o.ldwo = wo.stride(0); o.Hout = (int)Hout; o.oacc = oacc.data_ptr<float>();
   // past the fused kernel's one-pass limit: split attention partials (keys per split >= 128), merged
   // inside the o_proj launch
   at::Tensor part;
-  float *po = nullptr, *pm = nullptr, *pl = nullptr, *mo = nullptr;
-  if (Lmax > nxd::decode_attn_oproj_maxl()) {
-    const int64_t M = (int64_t)(Hq / Hkv) * T;
-    const int64_t rows = (int64_t)B * Hkv * ((Lmax + 127) / 128) * M;
-    part = at::empty({rows * (D + 2) + (int64_t)B * Hkv * M * D}, q.options().dtype(at::kFloat));
-    po = part.data_ptr<float>(); pm = po + rows * D; pl = pm + rows; mo = pl + rows;
+  if (a.Lmax > nxd::decode_attn_oproj_maxl()) {
+    const int64_t M = (int64_t)(a.Hq / a.Hkv) * a.T;
+    const int64_t rows = (int64_t)a.B * a.Hkv * ((a.Lmax + 127) / 128) * M;
+    part = at::empty({rows * (a.D + 2) + (int64_t)a.B * a.Hkv * M * a.D}, q.options().dtype(at::kFloat));
+    a.po = part.data_ptr<float>(); a.pm = a.po + rows * a.D; a.pl = a.pm + rows; o.mo = a.pl + rows;
   }
-  const int rc = nxd::decode_attn_oproj_launch(q.data_ptr(), qs, kc.data_ptr(), vc.data_ptr(), cs, ci, seq_len.data_ptr<int>(),
-                                               wo.data_ptr(), wo.stride(0), (int)Hout, oacc.data_ptr<float>(), po, pm, pl, mo, B, T,
-                                               Hq, Hkv, D, Lmax, (float)scale, cur_stream(),
-                                               window >= Lmax ? 0 : (int)window);
+  const int rc = nxd::decode_attn_oproj_launch(a, o);
   if (rc == -1) return false;
   check_rc(rc, "decode_attn_oproj");
   return true;
@@ -608,94 +616,65 @@ void decode_attn(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional<at::T
   bshd_strides(out, "out", os);
   // MXFP8 cache: the KV8 form of the MFMA kernel when it covers the call (M <= 16, D 64 / 128, contiguous
   // 16-byte aligned caches); otherwise both caches are dequantized into scratch bf16 caches and
-  // the bf16 kernels below run on those -- static shapes, capturable, slower
+  // the bf16 kernels run on those -- static shapes, capturable, slower
   TORCH_CHECK(k_scale.has_value() == v_scale.has_value(), "decode_attn: k_scale and v_scale go together");
-  const void *ksp = nullptr, *vsp = nullptr;
-  int64_t ss[3] = {0, 0, 0};
+  bool covered = false;
   if (k_scale.has_value()) {
     check_mx8(kc, *k_scale, "k_cache");
     check_mx8(vc, *v_scale, "v_cache");
     TORCH_CHECK(vc.sizes() == kc.sizes() && kc.device() == q.device() && vc.device() == q.device(), "cache shape / device mismatch");
     const int64_t D8 = kc.size(3), Hkv8 = kc.size(1);
-    const bool covered = Hkv8 > 0 && q.size(2) % Hkv8 == 0 && (q.size(2) / Hkv8) * q.size(1) <= 16 && (D8 == 64 || D8 == 128) &&
-                         kc.is_contiguous() && vc.is_contiguous() && k_scale->is_contiguous() && v_scale->is_contiguous();
-    if (!covered) {
-      kc = mx8_dequant(kc, *k_scale);
-      vc = mx8_dequant(vc, *v_scale);
-    } else {
-      ksp = k_scale->data_ptr();
-      vsp = v_scale->data_ptr();
-      for (int i = 0; i < 3; ++i) ss[i] = k_scale->stride(i);
-    }
+    covered = Hkv8 > 0 && q.size(2) % Hkv8 == 0 && (q.size(2) / Hkv8) * q.size(1) <= 16 && (D8 == 64 || D8 == 128) &&
+              kc.is_contiguous() && vc.is_contiguous() && k_scale->is_contiguous() && v_scale->is_contiguous();
   }
-  if (ksp != nullptr) {
+  // One call on resolved caches: bf16 (no scales), or MXFP8 codes the KV8 kernel covers.  The rules of
+  // the 128-key-chunk kernel apply where the cache is bf16: the KV8 kernel's are `covered` above.
+  // Returns the launcher's code (-4, with scales only: dequantize and come back).
+  const auto run = [&](const at::Tensor& kc, const at::Tensor& vc, const at::Tensor* ksc, const at::Tensor* vsc) {
+    const bool kv8 = ksc != nullptr;
+    if (!kv8) {
+      check_bf16(kc, "k_cache");
+      check_bf16(vc, "v_cache");
+      TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.sizes() == kc.sizes() && vc.is_contiguous(),
+                  "caches must be contiguous [B, Hkv, Lmax, D]");
+    }
     const int B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
     const int Hkv = kc.size(1), Lmax = kc.size(2);
-    TORCH_CHECK(kc.size(3) == D, "head dim mismatch");
-    TORCH_CHECK(nsplit >= 1 && nsplit * 128 >= Lmax, "nsplit * 128 must cover the cache length");
-    TORCH_CHECK(window >= 0, "window must be >= 0 (0: none)");
-    TORCH_CHECK(seq_len.scalar_type() == at::kInt && seq_len.numel() == B && seq_len.is_contiguous(), "seq_len must be int32 [B]");
-    const int* ci = nullptr;
-    if (cache_idx.has_value()) {
-      TORCH_CHECK(cache_idx->scalar_type() == at::kInt && cache_idx->numel() == B, "cache_idx must be int32 [B]");
-      ci = cache_idx->data_ptr<int>();
-    } else {
-      TORCH_CHECK(kc.size(0) >= B, "cache batch too small");
+    TORCH_CHECK(kc.size(3) == D && (kv8 || D == 64 || D == 128), kv8 ? "head dim mismatch" : "head dim mismatch (64/128)");
+    if (!kv8) {
+      TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "q heads must be a multiple of kv heads");
+      TORCH_CHECK((int64_t)(Hq / Hkv) * T <= 64, "decode supports (Hq/Hkv) * new_tokens <= 64");
     }
+    TORCH_CHECK(nsplit >= 1 && nsplit * 128 >= Lmax, "nsplit * 128 must cover the cache length");
+    nxd::DecodeAttnArgs a = decode_attn_args(q, qs, kc, vc, cache_idx, seq_len, scale, window);
     TORCH_CHECK(out.sizes() == q.sizes(), "out shape mismatch");
     TORCH_CHECK(os[2] % 8 == 0 || Hq == 1, "out head stride must keep 16-byte alignment");
+    a.out = out.data_ptr(); a.o_sb = os[0]; a.o_st = os[1]; a.o_sh = os[2];
     const int M = (Hq / Hkv) * T;
     auto opts = q.options().dtype(at::kFloat);
     at::Tensor po = at::empty({(int64_t)B * Hkv * nsplit * M * D}, opts);
     at::Tensor pm = at::empty({(int64_t)B * Hkv * nsplit * M}, opts);
     at::Tensor pl = at::empty({(int64_t)B * Hkv * nsplit * M}, opts);
-    const int64_t cs[3] = {kc.stride(0), kc.stride(1), kc.stride(2)};
-    const int rc = nxd::decode_attn_launch(q.data_ptr(), qs, kc.data_ptr(), vc.data_ptr(), cs, ci, seq_len.data_ptr<int>(),
-                                           po.data_ptr<float>(), pm.data_ptr<float>(), pl.data_ptr<float>(), nullptr,
-                                           out.data_ptr(), os, B, T, Hq, Hkv, D, (int)nsplit, (float)scale, cur_stream(),
-                                           window >= Lmax ? 0 : (int)window, ksp, vsp, ss);
-    if (rc != -4) {
-      check_rc(rc, "decode_attn (mxfp8)");
-      nxd::decode_attn_set_prefetch(nullptr, 0, nullptr, 0, 0);
-      return;
+    a.po = po.data_ptr<float>(); a.pm = pm.data_ptr<float>(); a.pl = pl.data_ptr<float>();
+    if (kv8) {
+      a.ksc = ksc->data_ptr(); a.vsc = vsc->data_ptr();
+      a.s_sb = ksc->stride(0); a.s_sh = ksc->stride(1); a.s_sl = ksc->stride(2);
     }
-    kc = mx8_dequant(kc, *k_scale);   // misaligned rows, or the MFMA kernel is switched off
-    vc = mx8_dequant(vc, *v_scale);
+    // split counters of the chunk kernel, which never reads an MXFP8 cache
+    int* counters = kv8 ? nullptr : decode_counters(q.device().index(), (int64_t)B * Hkv);
+    return nxd::decode_attn_launch(a, (int)nsplit, counters);
+  };
+  const char* what = "decode_attn (mxfp8)";
+  int rc = covered ? run(kc, vc, &*k_scale, &*v_scale) : -4;
+  if (rc == -4) {
+    if (k_scale.has_value()) {   // not covered, misaligned rows, or the MFMA kernel is switched off
+      kc = mx8_dequant(kc, *k_scale);
+      vc = mx8_dequant(vc, *v_scale);
+    }
+    what = "decode_attn";
+    rc = run(kc, vc, nullptr, nullptr);
   }
-  check_bf16(kc, "k_cache");
-  check_bf16(vc, "v_cache");
-  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.sizes() == kc.sizes() && vc.is_contiguous(),
-              "caches must be contiguous [B, Hkv, Lmax, D]");
-  const int B = q.size(0), T = q.size(1), Hq = q.size(2), D = q.size(3);
-  const int Hkv = kc.size(1), Lmax = kc.size(2);
-  TORCH_CHECK(kc.size(3) == D && (D == 64 || D == 128), "head dim mismatch (64/128)");
-  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "q heads must be a multiple of kv heads");
-  TORCH_CHECK((int64_t)(Hq / Hkv) * T <= 64, "decode supports (Hq/Hkv) * new_tokens <= 64");
-  TORCH_CHECK(nsplit >= 1 && nsplit * 128 >= Lmax, "nsplit * 128 must cover the cache length");
-  TORCH_CHECK(window >= 0, "window must be >= 0 (0: none)");
-  TORCH_CHECK(seq_len.scalar_type() == at::kInt && seq_len.numel() == B && seq_len.is_contiguous(), "seq_len must be int32 [B]");
-  const int* ci = nullptr;
-  if (cache_idx.has_value()) {
-    TORCH_CHECK(cache_idx->scalar_type() == at::kInt && cache_idx->numel() == B, "cache_idx must be int32 [B]");
-    ci = cache_idx->data_ptr<int>();
-  } else {
-    TORCH_CHECK(kc.size(0) >= B, "cache batch too small");
-  }
-  TORCH_CHECK(out.sizes() == q.sizes(), "out shape mismatch");
-  const int M = (Hq / Hkv) * T;
-  auto opts = q.options().dtype(at::kFloat);
-  at::Tensor po = at::empty({(int64_t)B * Hkv * nsplit * M * D}, opts);
-  at::Tensor pm = at::empty({(int64_t)B * Hkv * nsplit * M}, opts);
-  at::Tensor pl = at::empty({(int64_t)B * Hkv * nsplit * M}, opts);
-  const int64_t cs[3] = {kc.stride(0), kc.stride(1), kc.stride(2)};
-  (void)Lmax;
-  TORCH_CHECK(os[2] % 8 == 0 || Hq == 1, "out head stride must keep 16-byte alignment");
-  int* counters = decode_counters(q.device().index(), (int64_t)B * Hkv);
-  check_rc(nxd::decode_attn_launch(q.data_ptr(), qs, kc.data_ptr(), vc.data_ptr(), cs, ci, seq_len.data_ptr<int>(),
-                                   po.data_ptr<float>(), pm.data_ptr<float>(), pl.data_ptr<float>(), counters, out.data_ptr(),
-                                   os, B, T, Hq, Hkv, D, (int)nsplit, (float)scale, cur_stream(),
-                                   window >= Lmax ? 0 : (int)window, nullptr, nullptr, nullptr),
-           "decode_attn");
+  check_rc(rc, what);
   nxd::decode_attn_set_prefetch(nullptr, 0, nullptr, 0, 0);   // armed ranges never outlive one call
 }
 
@@ -719,13 +698,7 @@ void kv_cache_write(at::Tensor k, at::Tensor v, at::Tensor kc, at::Tensor vc, c1
     const int B = k.size(0), T = k.size(1), H = k.size(2), D = k.size(3);
     TORCH_CHECK(kc.size(1) == H && kc.size(3) == D && kc.device() == k.device(), "cache / new kv mismatch");
     TORCH_CHECK(pos.scalar_type() == at::kInt && pos.numel() == B, "pos must be int32 [B]");
-    const int* ci = nullptr;
-    if (cache_idx.has_value()) {
-      TORCH_CHECK(cache_idx->scalar_type() == at::kInt && cache_idx->numel() == B, "cache_idx must be int32 [B]");
-      ci = cache_idx->data_ptr<int>();
-    } else {
-      TORCH_CHECK(kc.size(0) >= B, "cache batch too small");
-    }
+    const int* ci = cache_rows(cache_idx, kc, B);
     check_rc(nxd::kv_write_mx8_launch(k.data_ptr(), v.data_ptr(), ks, kc.data_ptr(), vc.data_ptr(), k_scale->data_ptr(),
                                       v_scale->data_ptr(), ci, pos.data_ptr<int>(), B, (int)kc.size(0), T, H, D, (int)kc.size(2),
                                       cur_stream()),
@@ -738,13 +711,7 @@ void kv_cache_write(at::Tensor k, at::Tensor v, at::Tensor kc, at::Tensor vc, c1
   const int B = k.size(0), T = k.size(1), H = k.size(2), D = k.size(3);
   TORCH_CHECK(kc.size(1) == H && kc.size(3) == D && D % 8 == 0, "cache / new kv mismatch");
   TORCH_CHECK(pos.scalar_type() == at::kInt && pos.numel() == B, "pos must be int32 [B]");
-  const int* ci = nullptr;
-  if (cache_idx.has_value()) {
-    TORCH_CHECK(cache_idx->scalar_type() == at::kInt && cache_idx->numel() == B, "cache_idx must be int32 [B]");
-    ci = cache_idx->data_ptr<int>();
-  } else {
-    TORCH_CHECK(kc.size(0) >= B, "cache batch too small");
-  }
+  const int* ci = cache_rows(cache_idx, kc, B);
   const int64_t cs[3] = {kc.stride(0), kc.stride(1), kc.stride(2)};
   check_rc(nxd::kv_cache_write_launch(k.data_ptr(), v.data_ptr(), ks, kc.data_ptr(), vc.data_ptr(), cs, ci, pos.data_ptr<int>(),
                                       B, T, H, D, (int)kc.size(2), cur_stream()),

@@ -26,6 +26,7 @@
 // the down projection's residual epilogue, decode_fused.hip xadd / yadd) folds the accumulator into
 // the residual stream with the rounding of the unfused o_proj epilogue and zeroes it.
 #include "common.h"
+#include "decode_attn.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -35,6 +36,15 @@ namespace dattn {
 
 constexpr int KB = 64;            // keys per chunk (one wave)
 constexpr int KPS = 1024;         // most keys per workgroup split (one pass of 8 waves x 2 chunks)
+
+// Kernel variants: bits of attn_kernel's flags argument (their meaning is told at the kernel)
+enum : unsigned { FUSE = 1, WO_EARLY = 2, SYNC = 4, WIN = 8, KV8 = 16 };
+// D = 64: 8 waves (<= 2 chunks each per 1024-key split); D = 128: 4 waves (LDS: V tiles + merge)
+constexpr int waves(int D) { return D == 64 ? 8 : 4; }
+// dynamic LDS of attn_kernel: a V tile per wave, then the waves' O rows and (max, sum) for the merge
+constexpr size_t attn_lds(int D) {
+  return (size_t)waves(D) * KB * D * 2 + (size_t)waves(D) * 16 * D * 4 + (size_t)2 * waves(D) * 16 * 4;
+}
 
 struct Params {
   const uint16_t* q;
@@ -67,18 +77,18 @@ struct Params {
   // at entry and exit to trace[2 * blockIdx.x + {0, 1}]; null = off.  This is the trailing field whose
   // round-4 version aborted the decode tests: decode_attn2_launch built `Params p;` without value-
   // initialisation, so the field was stack garbage (non-null) there and the kernel stored through it
-  // (profiles/r4_decode_attn_trace_abort.txt).  Every launcher now value-initialises its Params.
+  // (profiles/r4_decode_attn_trace_abort.txt).  Both launchers now get their Params from make_params,
+  // the one place that builds it, value-initialised.
   uint64_t* trace;
   // SYNC (fused, long caches): per-(batch, kv head) arrival / done counters [2][kSyncHeads] (device
   // globals, zero at load, reset by the last workgroup of each head) and the bounded-spin error word
   unsigned* sync_cnt;
   int* sync_err;
   float* mo;          // SYNC: [B * Hkv, M, D] merged attention rows (the merger's hand-off)
-  // sliding window (0 = none, the WIN = false kernels; never with SYNC): query row at absolute position lim - 1 sees the keys
+  // sliding window (0 = none, the kernels without WIN; never with SYNC): query row at absolute position lim - 1 sees the keys
   // max(0, lim - window) <= key < lim, and the workgroup's sweep starts at the first 64-key chunk any row
   // of this sequence can see (read from the device seq_len: static shapes, graph-capturable) -- the
-  // launchers size kps / nsplit by the window, not the cache (window_span).  Value-initialised to 0
-  // by every launcher, as the rule above asks.
+  // launchers size kps / nsplit by the window, not the cache (window_span).
   int window;
   // KV8 (MXFP8 cache, ops/decode.py): kc / vc are E4M3 code bytes (c_sb / c_sh / c_sl in bytes) and these
   // the E8M0 block-scale bytes [Bc, Hkv, Lmax, D / 32] with their strides; null for a bf16 cache.
@@ -183,8 +193,14 @@ __device__ __forceinline__ void oproj_tail(const Params& p, const float* of, con
 // into the same bf16 LDS tile, so the transposed reads, the softmax, P.V and the merge see the values a
 // bf16 cache holding the dequantized data would give them, in the same order: the outputs are equal
 // bit for bit.
-template <int D, int NWV, bool FUSE, bool WO_LATE = true, bool SYNC = false, bool WIN = false, bool KV8 = false>
-__global__ void __launch_bounds__(64 * NWV) attn_kernel(Params p) {
+// F: the variant's flags.  WO_EARLY (with FUSE) issues the Wo block before the K / V loads (WO_LATE below
+// is its absence, the default).
+template <int D, unsigned F>
+__global__ void __launch_bounds__(64 * waves(D)) attn_kernel(Params p) {
+  constexpr int NWV = waves(D);
+  constexpr bool FUSE = (F & dattn::FUSE) != 0, WO_LATE = (F & dattn::WO_EARLY) == 0, SYNC = (F & dattn::SYNC) != 0;
+  constexpr bool WIN = (F & dattn::WIN) != 0, KV8 = (F & dattn::KV8) != 0;
+  static_assert(FUSE || WO_LATE, "WO_EARLY is a FUSE form");
   static_assert(!SYNC || FUSE, "SYNC is a FUSE form");
   static_assert(!WIN || !SYNC, "no SYNC form with a sliding window");
   static_assert(!KV8 || !FUSE, "the fused attention + o_proj reads a bf16 cache");
@@ -584,8 +600,9 @@ static int window_span(int Lmax, int T, int& window) {
 // output the o_proj GEMV would read) -> this workgroup's o_proj partial, fp32 atomics into oacc: the
 // long-context form of FUSE (one launch instead of the merge + o_proj pair).  Grid (batch, kv head,
 // R row chunks), the split weights of each query row in LDS.
-template <int D, int NWV>
-__global__ void __launch_bounds__(64 * NWV) merge_oproj_kernel(Params p) {
+template <int D>
+__global__ void __launch_bounds__(64 * waves(D)) merge_oproj_kernel(Params p) {
+  constexpr int NWV = waves(D);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* of = reinterpret_cast<float*>(smem);   // [M][D] merged attention output
   float* wts = of + 16 * D;                     // [nsplit][16] normalised split weights
@@ -698,6 +715,41 @@ static const void* g_pf[2] = {nullptr, nullptr};
 static int64_t g_pf_bytes[2] = {0, 0};
 static int g_pf_wgs = 0;
 
+// The kernel arguments every launch shares, from the call's description (window as window_span left
+// it); what only one form needs -- splits, grid, prefetch ranges, the o_proj and SYNC fields -- is the
+// launcher's to add.  Value-initialised: a field nobody sets is zero / null (see Params::trace).
+static Params make_params(const DecodeAttnArgs& a) {
+  Params p{};
+  p.q = (const uint16_t*)a.q; p.q_sb = a.q_sb; p.q_st = a.q_st; p.q_sh = a.q_sh;
+  p.kc = (const uint16_t*)a.kc; p.vc = (const uint16_t*)a.vc;
+  p.c_sb = a.c_sb; p.c_sh = a.c_sh; p.c_sl = a.c_sl;
+  p.ksc = (const uint8_t*)a.ksc; p.vsc = (const uint8_t*)a.vsc;
+  p.s_sb = a.s_sb; p.s_sh = a.s_sh; p.s_sl = a.s_sl;
+  p.cache_idx = a.cache_idx; p.seq_len = a.seq_len;
+  p.out = (uint16_t*)a.out; p.o_sb = a.o_sb; p.o_st = a.o_st; p.o_sh = a.o_sh;
+  p.po = a.po; p.pm = a.pm; p.pl = a.pl;
+  p.B = a.B; p.T = a.T; p.Hq = a.Hq; p.Hkv = a.Hkv;
+  p.window = a.window;
+  p.scale_log2 = a.scale * 1.4426950408889634f;
+  p.trace = g_trace;
+  return p;
+}
+
+// One launch of a kernel with dynamic LDS: raise the kernel's limit to it (every time: cheap, and
+// there is no first-launch state to keep), launch on 64 * waves(D) threads, return the HIP error.
+static int launch(void (*kernel)(Params), int D, dim3 grid, size_t lds, hipStream_t stream, const Params& p) {
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, grid, dim3(64 * waves(D)), lds, stream, p);
+  return (int)hipGetLastError();
+}
+template <unsigned F>
+static int launch_attn(int D, dim3 grid, hipStream_t stream, const Params& p) {
+  return launch(D == 64 ? attn_kernel<64, F> : attn_kernel<128, F>, D, grid, attn_lds(D), stream, p);
+}
+static int launch_merge_oproj(int D, dim3 grid, size_t lds, hipStream_t stream, const Params& p) {
+  return launch(D == 64 ? merge_oproj_kernel<64> : merge_oproj_kernel<128>, D, grid, lds, stream, p);
+}
+
 }  // namespace dattn
 
 // Opt-in phase trace of the following decode attention launches (eager or captured: the pointer is
@@ -711,87 +763,43 @@ void decode_attn_set_prefetch(const void* a, int64_t a_bytes, const void* b, int
 }
 
 // Returns -1 when the shape is not covered (caller falls back to the 128-key-chunk kernel).
-// window > 0: sliding-window attention (Params::window); kps / nsplit follow the window's key span.
-// ksc / vsc non-null: MXFP8 cache (KV8) -- kc / vc are the code bytes with byte strides cs (16-byte
-// aligned rows), ksc / vsc the scale bytes with strides ss (rows aligned to their D / 32 bytes).
-int decode_attn2_launch(const void* q, const int64_t* qs, const void* kc, const void* vc, const int64_t* cs,
-                        const int* cache_idx, const int* seq_len, float* po, float* pm, float* pl, void* out,
-                        const int64_t* os, int B, int T, int Hq, int Hkv, int D, int Lmax, float scale, int* nsplit_out,
-                        hipStream_t stream, int window, const void* ksc, const void* vsc, const int64_t* ss) {
-  if (Hkv <= 0 || Hq % Hkv) return -1;
-  const int M = (Hq / Hkv) * T;
+// a.window > 0: sliding-window attention (Params::window); kps / nsplit follow the window's key span.
+// a.ksc / a.vsc non-null: MXFP8 cache (KV8) -- kc / vc are the code bytes with byte strides (16-byte
+// aligned rows), ksc / vsc the scale bytes with their strides (rows aligned to their D / 32 bytes).
+int decode_attn2_launch(DecodeAttnArgs a, int* nsplit_out) {
+  using namespace dattn;
+  if (a.Hkv <= 0 || a.Hq % a.Hkv) return -1;
+  const int M = (a.Hq / a.Hkv) * a.T, D = a.D;
   if (M > 16 || (D != 64 && D != 128)) return -1;
-  if ((ksc != nullptr) != (vsc != nullptr)) return -1;
-  if (ksc != nullptr) {
-    const auto al = [](const void* a, int64_t n) { return reinterpret_cast<uintptr_t>(a) % n == 0; };
+  const bool kv8 = a.ksc != nullptr;
+  if (kv8 != (a.vsc != nullptr)) return -1;
+  if (kv8) {
+    const auto al = [](const void* ptr, int64_t n) { return reinterpret_cast<uintptr_t>(ptr) % n == 0; };
     const int sb = D / 32;
-    if (ss == nullptr || !al(kc, 16) || !al(vc, 16) || cs[0] % 16 || cs[1] % 16 || cs[2] % 16 || !al(ksc, sb) || !al(vsc, sb) ||
-        ss[0] % sb || ss[1] % sb || ss[2] % sb)
+    if (!al(a.kc, 16) || !al(a.vc, 16) || a.c_sb % 16 || a.c_sh % 16 || a.c_sl % 16 || !al(a.ksc, sb) || !al(a.vsc, sb) ||
+        a.s_sb % sb || a.s_sh % sb || a.s_sl % sb)
       return -1;
   }
-  const int Leff = dattn::window_span(Lmax, T, window);
-  dattn::Params p{};   // value-initialised: every field a launcher does not set is zero / null
-  p.q = (const uint16_t*)q; p.q_sb = qs[0]; p.q_st = qs[1]; p.q_sh = qs[2];
-  p.kc = (const uint16_t*)kc; p.vc = (const uint16_t*)vc;
-  p.c_sb = cs[0]; p.c_sh = cs[1]; p.c_sl = cs[2];
-  p.cache_idx = cache_idx; p.seq_len = seq_len;
-  p.out = (uint16_t*)out; p.o_sb = os[0]; p.o_st = os[1]; p.o_sh = os[2];
-  p.po = po; p.pm = pm; p.pl = pl;
-  p.B = B; p.T = T; p.Hq = Hq; p.Hkv = Hkv;
-  const int kps = dattn::keys_per_split(Leff, B, Hkv);
-  p.kps = kps;
-  p.nsplit = (Leff + kps - 1) / kps;
-  p.window = window;
-  p.scale_log2 = scale * 1.4426950408889634f;
+  const int Leff = window_span(a.Lmax, a.T, a.window);
+  Params p = make_params(a);
+  p.kps = keys_per_split(Leff, a.B, a.Hkv);
+  p.nsplit = (Leff + p.kps - 1) / p.kps;
   *nsplit_out = p.nsplit;
-  // D = 64: 8 waves (<= 2 chunks each per 1024-key split); D = 128: 4 waves (LDS: V tiles + merge)
-  const int nwv = D == 64 ? 8 : 4;
-  const size_t lds = (size_t)nwv * dattn::KB * D * 2 + (size_t)nwv * 16 * D * 4 + (size_t)2 * nwv * 16 * 4;
-  p.attn_wgs = B * Hkv * p.nsplit;
-  p.trace = dattn::g_trace;
+  p.attn_wgs = a.B * a.Hkv * p.nsplit;
   int pf_wgs = 0;
   for (int r = 0; r < 2; ++r) {
     // 16-B aligned start, whole chunks only (a prefetch never needs the ragged tail)
-    const bool ok = dattn::g_pf[r] && (reinterpret_cast<uintptr_t>(dattn::g_pf[r]) & 15) == 0 && dattn::g_pf_bytes[r] >= 16;
-    p.pf[r] = ok ? static_cast<const u32x4_t*>(dattn::g_pf[r]) : nullptr;
-    p.pf_n16[r] = ok ? dattn::g_pf_bytes[r] / 16 : 0;
-    if (ok) pf_wgs = dattn::g_pf_wgs > 0 ? dattn::g_pf_wgs : 256;
+    const bool ok = g_pf[r] && (reinterpret_cast<uintptr_t>(g_pf[r]) & 15) == 0 && g_pf_bytes[r] >= 16;
+    p.pf[r] = ok ? static_cast<const u32x4_t*>(g_pf[r]) : nullptr;
+    p.pf_n16[r] = ok ? g_pf_bytes[r] / 16 : 0;
+    if (ok) pf_wgs = g_pf_wgs > 0 ? g_pf_wgs : 256;
   }
-  dattn::g_pf[0] = dattn::g_pf[1] = nullptr;
-  dattn::g_pf_bytes[0] = dattn::g_pf_bytes[1] = 0;
-  const dim3 grid(p.attn_wgs + pf_wgs), block(64 * nwv);
-  if (ksc != nullptr) {   // MXFP8 cache: the KV8 instantiations (same LDS as the bf16 ones)
-    p.ksc = (const uint8_t*)ksc; p.vsc = (const uint8_t*)vsc;
-    p.s_sb = ss[0]; p.s_sh = ss[1]; p.s_sl = ss[2];
-    if (window && D == 64) {
-      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, false, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((dattn::attn_kernel<64, 8, false, true, false, true, true>), grid, block, lds, stream, p);
-    } else if (window) {
-      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<128, 4, false, true, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((dattn::attn_kernel<128, 4, false, true, false, true, true>), grid, block, lds, stream, p);
-    } else if (D == 64) {
-      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, false, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((dattn::attn_kernel<64, 8, false, true, false, false, true>), grid, block, lds, stream, p);
-    } else {
-      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<128, 4, false, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((dattn::attn_kernel<128, 4, false, true, false, false, true>), grid, block, lds, stream, p);
-    }
-  } else if (window) {
-    if (D == 64) {
-      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((dattn::attn_kernel<64, 8, false, true, false, true>), grid, block, lds, stream, p);
-    } else {
-      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<128, 4, false, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((dattn::attn_kernel<128, 4, false, true, false, true>), grid, block, lds, stream, p);
-    }
-  } else if (D == 64) {
-    (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((dattn::attn_kernel<64, 8, false>), grid, block, lds, stream, p);
-  } else {
-    (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<128, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((dattn::attn_kernel<128, 4, false>), grid, block, lds, stream, p);
-  }
-  return (int)hipGetLastError();
+  g_pf[0] = g_pf[1] = nullptr;
+  g_pf_bytes[0] = g_pf_bytes[1] = 0;
+  const dim3 grid(p.attn_wgs + pf_wgs);
+  if (kv8)   // MXFP8 cache: the KV8 instantiations (same LDS as the bf16 ones)
+    return a.window ? launch_attn<WIN | KV8>(D, grid, a.stream, p) : launch_attn<KV8>(D, grid, a.stream, p);
+  return a.window ? launch_attn<WIN>(D, grid, a.stream, p) : launch_attn<0>(D, grid, a.stream, p);
 }
 
 namespace dattn {
@@ -826,25 +834,23 @@ int decode_attn_oproj_maxl() {
 // the whole cache; past that the split attention, whose keys per split fill the GPU, + merge + o_proj
 // launches win -- 0.726 vs 0.774 ms/token at the notebook's 2,304-key cache,
 // profiles/r6_decode/attn_split_ab.txt), M = G*T <= 16, D in {64, 128}, Wo blocks of <= 4 register
-// passes.  window > 0 (sliding window): Lmax above is the window's key span (window_span), and the
-// SYNC form is never taken.
-int decode_attn_oproj_launch(const void* q, const int64_t* qs, const void* kc, const void* vc, const int64_t* cs,
-                             const int* cache_idx, const int* seq_len, const void* wo, int64_t ldwo, int Hout, float* oacc,
-                             float* po, float* pm, float* pl, float* mo, int B, int T, int Hq, int Hkv, int D, int Lmax,
-                             float scale, hipStream_t stream, int window) {
-  if (Hkv <= 0 || Hq % Hkv) return -1;
-  const int G = Hq / Hkv, M = G * T;
+// passes, a bf16 cache.  a.window > 0 (sliding window): Lmax above is the window's key span
+// (window_span), and the SYNC form is never taken.
+int decode_attn_oproj_launch(DecodeAttnArgs a, const DecodeOprojArgs& o) {
+  using namespace dattn;
+  if (a.Hkv <= 0 || a.Hq % a.Hkv || a.ksc != nullptr || a.vsc != nullptr) return -1;
+  const int B = a.B, Hkv = a.Hkv, D = a.D, Hout = o.Hout;
+  const int G = a.Hq / Hkv, M = G * a.T;
   const int maxl = decode_attn_oproj_maxl();
   // with a sliding window every size below is that of the window's key span, not of the cache: the
   // one-pass form serves any cache whose window fits maxl
-  const int Lcache = Lmax;
-  Lmax = dattn::window_span(Lcache, T, window);
+  const int Lcache = a.Lmax;
+  const int Lmax = window_span(Lcache, a.T, a.window);
   // past maxl: split attention into the partials, then merge + o_proj (needs the partial buffers:
   // [B * Hkv * ceil(Lmax / 128) * M] rows of D, plus the two stats)
-  const bool split = Lmax > maxl && po != nullptr && dattn::keys_per_split(Lmax, B, Hkv) < Lmax;
-  if (M > 16 || (D != 64 && D != 128) || (Lmax > maxl && !split) || (G * D) % 32 || ldwo % 8) return -1;
-  const int nwv = D == 64 ? 8 : 4;
-  const int nt = 64 * nwv, tpr = (G * D) / 32;
+  const bool split = Lmax > maxl && a.po != nullptr && keys_per_split(Lmax, B, Hkv) < Lmax;
+  if (M > 16 || (D != 64 && D != 128) || (Lmax > maxl && !split) || (G * D) % 32 || o.ldwo % 8) return -1;
+  const int nt = 64 * waves(D), tpr = (G * D) / 32;
   if (tpr > 64 || 64 % tpr || nt % tpr) return -1;
   const int rpp = nt / tpr;
   // row chunks per kv head: fill >= target workgroups (NXD_DECODE_OPROJ_WGS, default 256), at most 4
@@ -859,103 +865,59 @@ int decode_attn_oproj_launch(const void* q, const int64_t* qs, const void* kc, c
   while (Hout % R == 0 && (Hout / R) % rpp == 0 && Hout / R / rpp > 4 && Hout % (2 * R) == 0 && (Hout / (2 * R)) % rpp == 0)
     R *= 2;
   if (Hout % R || (Hout / R) % rpp || Hout / R / rpp > 4 || Hout / R / rpp < 1) return -1;
-  dattn::Params p{};
-  p.q = (const uint16_t*)q; p.q_sb = qs[0]; p.q_st = qs[1]; p.q_sh = qs[2];
-  p.kc = (const uint16_t*)kc; p.vc = (const uint16_t*)vc;
-  p.c_sb = cs[0]; p.c_sh = cs[1]; p.c_sl = cs[2];
-  p.cache_idx = cache_idx; p.seq_len = seq_len;
-  p.B = B; p.T = T; p.Hq = Hq; p.Hkv = Hkv; p.nsplit = 1;
-  p.window = window;
-  p.scale_log2 = scale * 1.4426950408889634f;
-  p.wo = (const uint16_t*)wo; p.ldwo = ldwo; p.oacc = oacc; p.Hout = Hout; p.R = R; p.NP = Hout / R / rpp;
+  Params p = make_params(a);
+  p.nsplit = 1;
+  p.wo = (const uint16_t*)o.wo; p.ldwo = o.ldwo; p.oacc = o.oacc; p.Hout = Hout; p.R = R; p.NP = Hout / R / rpp;
   p.attn_wgs = B * Hkv * R;
-  p.trace = dattn::g_trace;
-  const dim3 grid(p.attn_wgs), block(nt);
-  if (dattn::g_sync_on < 0) {
+  const dim3 grid(p.attn_wgs);
+  if (g_sync_on < 0) {
     const char* e = getenv("NXD_DECODE_ATTN_SYNC");
-    dattn::g_sync_on = e ? (atoi(e) != 0) : 0;
+    g_sync_on = e ? (atoi(e) != 0) : 0;
   }
-  const bool sync_on = dattn::g_sync_on != 0;
+  const bool sync_on = g_sync_on != 0;
   static const int n_cu = [] {
     int dev = 0, n = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n;
   }();
-  if (split && sync_on && window == 0 && mo != nullptr && B * Hkv <= dattn::kSyncHeads && (int)grid.x <= n_cu) {
+  if (split && sync_on && a.window == 0 && o.mo != nullptr && B * Hkv <= kSyncHeads && (int)grid.x <= n_cu) {
     // one launch: workgroup r of a head computes key split r (>= 128 keys, the partial buffers hold
     // Lmax / 128 splits), then merges the head's splits and runs its o_proj slice (SYNC above)
     int kps = (Lmax + R - 1) / R;
-    kps = (kps + dattn::KB - 1) / dattn::KB * dattn::KB;
+    kps = (kps + KB - 1) / KB * KB;
     kps = kps < 128 ? 128 : kps;
     const int ns = (Lmax + kps - 1) / kps;
-    const size_t lds = (size_t)nwv * dattn::KB * D * 2 + (size_t)nwv * 16 * D * 4 + (size_t)2 * nwv * 16 * 4;
-    if (ns <= R && (size_t)16 * D * 4 + (size_t)ns * 16 * 4 <= (size_t)nwv * dattn::KB * D * 2) {
-      static unsigned* cnt = [] { void* a = nullptr; (void)hipGetSymbolAddress(&a, HIP_SYMBOL(dattn::g_sync_cnt)); return (unsigned*)a; }();
-      static int* err = [] { void* a = nullptr; (void)hipGetSymbolAddress(&a, HIP_SYMBOL(dattn::g_sync_err)); return (int*)a; }();
-      p.kps = kps; p.nsplit = ns; p.po = po; p.pm = pm; p.pl = pl; p.sync_cnt = cnt; p.sync_err = err;
-      p.mo = mo;
-      if (D == 64) {
-        (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((dattn::attn_kernel<64, 8, true, true, true>), grid, block, lds, stream, p);
-      } else {
-        (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<128, 4, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((dattn::attn_kernel<128, 4, true, true, true>), grid, block, lds, stream, p);
-      }
-      return (int)hipGetLastError();
+    if (ns <= R && (size_t)16 * D * 4 + (size_t)ns * 16 * 4 <= (size_t)waves(D) * KB * D * 2) {
+      static unsigned* cnt = [] { void* s = nullptr; (void)hipGetSymbolAddress(&s, HIP_SYMBOL(g_sync_cnt)); return (unsigned*)s; }();
+      static int* err = [] { void* s = nullptr; (void)hipGetSymbolAddress(&s, HIP_SYMBOL(g_sync_err)); return (int*)s; }();
+      p.kps = kps; p.nsplit = ns; p.sync_cnt = cnt; p.sync_err = err; p.mo = o.mo;
+      return launch_attn<FUSE | SYNC>(D, grid, a.stream, p);
     }
   }
   if (split) {
-    const int kps = dattn::keys_per_split(Lmax, B, Hkv), ns = (Lmax + kps - 1) / kps;
+    const int kps = keys_per_split(Lmax, B, Hkv), ns = (Lmax + kps - 1) / kps;
     const size_t mlds = (size_t)16 * D * 4 + (size_t)ns * 16 * 4 + (size_t)2 * 16 * D * 4;
     if (mlds > 64 * 1024) return -1;
+    // the attention rows stay in the partials: no output, and the cache's own capacity (the attention
+    // launch derives the window's span itself)
+    DecodeAttnArgs s = a;
+    s.Lmax = Lcache;
+    s.out = nullptr;
     int ns2 = 0;
-    const int64_t no_out[3] = {0, 0, 0};
-    const int rc = decode_attn2_launch(q, qs, kc, vc, cs, cache_idx, seq_len, po, pm, pl, nullptr, no_out, B, T, Hq, Hkv,
-                                       D, Lcache, scale, &ns2, stream, window, nullptr, nullptr, nullptr);
+    const int rc = decode_attn2_launch(s, &ns2);
     if (rc != 0) return rc;
     if (ns2 != ns) return 3;   // the attention launch split differently: never write the output through null
-    p.nsplit = ns; p.po = po; p.pm = pm; p.pl = pl;
-    if (D == 64) {
-      (void)hipFuncSetAttribute((const void*)dattn::merge_oproj_kernel<64, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds);
-      hipLaunchKernelGGL((dattn::merge_oproj_kernel<64, 8>), grid, block, mlds, stream, p);
-    } else {
-      (void)hipFuncSetAttribute((const void*)dattn::merge_oproj_kernel<128, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds);
-      hipLaunchKernelGGL((dattn::merge_oproj_kernel<128, 4>), grid, block, mlds, stream, p);
-    }
-    return (int)hipGetLastError();
+    p.nsplit = ns;
+    return launch_merge_oproj(D, grid, mlds, a.stream, p);
   }
-  const size_t lds = (size_t)nwv * dattn::KB * D * 2 + (size_t)nwv * 16 * D * 4 + (size_t)2 * nwv * 16 * 4;
   static const bool wo_late = [] {
     const char* e = getenv("NXD_DECODE_WO_LATE");
     return e ? atoi(e) != 0 : true;
   }();
-  if (window) {   // the Wo block always after the first K / V loads
-    if (D == 64) {
-      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((dattn::attn_kernel<64, 8, true, true, false, true>), grid, block, lds, stream, p);
-    } else {
-      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<128, 4, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((dattn::attn_kernel<128, 4, true, true, false, true>), grid, block, lds, stream, p);
-    }
-  } else if (D == 64) {
-    if (wo_late) {
-      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((dattn::attn_kernel<64, 8, true, true>), grid, block, lds, stream, p);
-    } else {
-      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<64, 8, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((dattn::attn_kernel<64, 8, true, false>), grid, block, lds, stream, p);
-    }
-  } else {
-    if (wo_late) {
-      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<128, 4, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((dattn::attn_kernel<128, 4, true, true>), grid, block, lds, stream, p);
-    } else {
-      (void)hipFuncSetAttribute((const void*)dattn::attn_kernel<128, 4, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((dattn::attn_kernel<128, 4, true, false>), grid, block, lds, stream, p);
-    }
-  }
-  return (int)hipGetLastError();
+  if (a.window) return launch_attn<FUSE | WIN>(D, grid, a.stream, p);   // the Wo block always after the first K / V loads
+  return wo_late ? launch_attn<FUSE>(D, grid, a.stream, p) : launch_attn<FUSE | WO_EARLY>(D, grid, a.stream, p);
 }
 
 }  // namespace nxd
+

@@ -14,6 +14,7 @@
 //    32-bit keys (no full sort of the 128k vocabulary), then softmax / CDF / uniform draw over
 //    the k survivors in LDS.
 #include "common.h"
+#include "decode_attn.h"
 
 namespace nxd {
 namespace dec {
@@ -524,79 +525,59 @@ __global__ void __launch_bounds__(1024) topk_sample_kernel(const T* __restrict__
 
 }  // namespace dec
 
-int decode_attn2_launch(const void*, const int64_t*, const void*, const void*, const int64_t*, const int*, const int*,
-                        float*, float*, float*, void*, const int64_t*, int, int, int, int, int, int, float, int*, hipStream_t,
-                        int, const void*, const void*, const int64_t*);
-
 static int g_attn_v2 = [] { const char* e = getenv("NXD_DECODE_ATTN_V2"); return e ? atoi(e) : 1; }();
 void decode_attn_set_v2(int v) { g_attn_v2 = v; }
 
-int decode_attn_launch(const void* q, const int64_t* qs, const void* kc, const void* vc, const int64_t* cs,
-                       const int* cache_idx, const int* seq_len, float* po, float* pm, float* pl, int* counters, void* out,
-                       const int64_t* os, int B, int T, int Hq, int Hkv, int D, int nsplit, float scale, hipStream_t stream,
-                       int window, const void* ksc, const void* vsc, const int64_t* ss) {
+// merge_kernel over the partials p describes -> out
+static void launch_merge(const dec::DecodeParams& p, const DecodeAttnArgs& a) {
+  const int M = (p.Hq / p.Hkv) * p.T;
+  const size_t mlds = (size_t)((M + 3) & ~3) * 4 + (size_t)4 * 8 * a.D * 4 + (size_t)p.nsplit * M * 4;
+  const auto kernel = a.D == 64 ? dec::merge_kernel<64> : dec::merge_kernel<128>;
+  if (mlds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds);
+  hipLaunchKernelGGL(kernel, dim3(p.B * p.Hkv), dim3(256), mlds, a.stream, p, (uint16_t*)a.out, a.o_sb, a.o_st, a.o_sh);
+}
+
+int decode_attn_launch(DecodeAttnArgs a, int nsplit, int* counters) {
   using namespace dec;
-  if (Hkv <= 0 || Hq % Hkv) return -1;
-  const int M = (Hq / Hkv) * T;
-  if (window < 0 || window >= nsplit * kChunk) window = 0;   // covers the cache: no window
+  if (a.Hkv <= 0 || a.Hq % a.Hkv) return -1;
+  const int M = (a.Hq / a.Hkv) * a.T, D = a.D;
+  a.Lmax = nsplit * kChunk;   // what the partial buffers hold, and what both kernels' splits cover
+  if (a.window < 0 || a.window >= a.Lmax) a.window = 0;   // covers the cache: no window
   // MXFP8 cache (ksc / vsc: the scale bytes, kc / vc the codes): only the MFMA kernel reads it; -4 tells
   // the caller to dequantize (mx8_dequant) and come back with a bf16 cache
-  const bool kv8 = ksc != nullptr || vsc != nullptr;
+  const bool kv8 = a.ksc != nullptr || a.vsc != nullptr;
   if (kv8 && !g_attn_v2) return -4;
+  // fused_merge and window stay 0 for the merge after the MFMA kernel; the chunk kernel sets its own
+  DecodeParams p{};
+  p.q = (const uint16_t*)a.q; p.q_sb = a.q_sb; p.q_st = a.q_st; p.q_sh = a.q_sh;
+  p.kc = (const uint16_t*)a.kc; p.vc = (const uint16_t*)a.vc;
+  p.c_sb = a.c_sb; p.c_sh = a.c_sh; p.c_sl = a.c_sl;
+  p.cache_idx = a.cache_idx; p.seq_len = a.seq_len; p.po = a.po; p.pm = a.pm; p.pl = a.pl;
+  p.B = a.B; p.T = a.T; p.Hq = a.Hq; p.Hkv = a.Hkv; p.scale = a.scale;
   // small query groups: the MFMA flash-decoding kernel (decode_attn.hip), merge only past 1024 keys
   if (g_attn_v2) {
-    int ns2 = 0;
-    const int rc = decode_attn2_launch(q, qs, kc, vc, cs, cache_idx, seq_len, po, pm, pl, out, os, B, T, Hq, Hkv, D,
-                                       nsplit * kChunk, scale, &ns2, stream, window, ksc, vsc, ss);
+    const int rc = decode_attn2_launch(a, &p.nsplit);
     if (kv8 && rc == -1) return -4;
-    if (rc == 0 && ns2 > 1) {
-      DecodeParams mp{};
-      mp.q = (const uint16_t*)q; mp.q_sb = qs[0]; mp.q_st = qs[1]; mp.q_sh = qs[2];
-      mp.kc = (const uint16_t*)kc; mp.vc = (const uint16_t*)vc;
-      mp.c_sb = cs[0]; mp.c_sh = cs[1]; mp.c_sl = cs[2];
-      mp.cache_idx = cache_idx; mp.seq_len = seq_len; mp.po = po; mp.pm = pm; mp.pl = pl;
-      mp.B = B; mp.T = T; mp.Hq = Hq; mp.Hkv = Hkv; mp.nsplit = ns2; mp.scale = scale; mp.fused_merge = 0;
-      const size_t mlds = (size_t)((M + 3) & ~3) * 4 + (size_t)4 * 8 * D * 4 + (size_t)ns2 * M * 4;
-      if (D == 64)
-        hipLaunchKernelGGL(merge_kernel<64>, dim3(B * Hkv), dim3(256), mlds, stream, mp, (uint16_t*)out, os[0], os[1], os[2]);
-      else
-        hipLaunchKernelGGL(merge_kernel<128>, dim3(B * Hkv), dim3(256), mlds, stream, mp, (uint16_t*)out, os[0], os[1], os[2]);
+    if (rc == 0 && p.nsplit > 1) {
+      launch_merge(p, a);
       return (int)hipGetLastError();
     }
     if (rc != -1) return rc;   // -1: shape not covered by the MFMA kernel
   }
-  DecodeParams p{};
-  p.q = (const uint16_t*)q; p.q_sb = qs[0]; p.q_st = qs[1]; p.q_sh = qs[2];
-  p.kc = (const uint16_t*)kc; p.vc = (const uint16_t*)vc;
-  p.c_sb = cs[0]; p.c_sh = cs[1]; p.c_sl = cs[2];
-  p.cache_idx = cache_idx; p.seq_len = seq_len; p.po = po; p.pm = pm; p.pl = pl;
-  p.B = B; p.T = T; p.Hq = Hq; p.Hkv = Hkv; p.nsplit = nsplit; p.scale = scale; p.window = window;
+  p.nsplit = nsplit;
+  p.window = a.window;
   // separate merge launch by default: the fused last-workgroup merge needs agent-scope fences (L2
   // write-back / invalidate across the 8 XCDs), measured 2-3x slower on MI355X (tools/bench_decode.py)
   static const int mode = [] { const char* e = getenv("NXD_DECODE_FUSED_MERGE"); return e ? atoi(e) : 0; }();
   p.fused_merge = mode;
   const size_t lds = (size_t)M * D * 4 + (size_t)M * kChunk * 4 + (size_t)4 * 8 * D * 4 + (size_t)nsplit * M * 4;
   if (lds > 160 * 1024) return -3;
-  const dim3 grid(B * Hkv * nsplit);
-  if (D == 64) {
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(attn_kernel<64>, grid, dim3(256), lds, stream, p, counters, (uint16_t*)out, os[0], os[1], os[2]);
-  } else if (D == 128) {
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)attn_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(attn_kernel<128>, grid, dim3(256), lds, stream, p, counters, (uint16_t*)out, os[0], os[1], os[2]);
-  } else {
-    return -2;
-  }
-  if (!p.fused_merge) {
-    const size_t mlds = (size_t)((M + 3) & ~3) * 4 + (size_t)4 * 8 * D * 4 + (size_t)nsplit * M * 4;
-    if (D == 64) {
-      if (mlds > 64 * 1024) (void)hipFuncSetAttribute((const void*)merge_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds);
-      hipLaunchKernelGGL(merge_kernel<64>, dim3(B * Hkv), dim3(256), mlds, stream, p, (uint16_t*)out, os[0], os[1], os[2]);
-    } else {
-      if (mlds > 64 * 1024) (void)hipFuncSetAttribute((const void*)merge_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds);
-      hipLaunchKernelGGL(merge_kernel<128>, dim3(B * Hkv), dim3(256), mlds, stream, p, (uint16_t*)out, os[0], os[1], os[2]);
-    }
-  }
+  if (D != 64 && D != 128) return -2;
+  const auto kernel = D == 64 ? attn_kernel<64> : attn_kernel<128>;
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, dim3(a.B * a.Hkv * nsplit), dim3(256), lds, a.stream, p, counters, (uint16_t*)a.out, a.o_sb,
+                     a.o_st, a.o_sh);
+  if (!p.fused_merge) launch_merge(p, a);
   return (int)hipGetLastError();
 }
 

@@ -264,9 +264,10 @@ def test_fused_attention_oproj_matches_two_launches(monkeypatch, hidden, heads, 
 @pytest.mark.parametrize("hidden,heads,kv", [(2048, 32, 8), (1024, 8, 2)])   # D = 64, 128
 def test_fused_attention_oproj_long_context(monkeypatch, hidden, heads, kv):
     """The fused attention + o_proj launches on a cache past one 1,024-key split (the notebook config's
-    2,048-token context + 256 new) -- every workgroup walking the whole cache; the default single launch
-    whose workgroups each take a key split, wait for the head's partials and merge them; and the split
-    attention launch whose partials the o_proj launch merges -- one decode step each against the split
+    2,048-token context + 256 new) -- every workgroup walking the whole cache; the opt-in single launch
+    (NXD_DECODE_ATTN_SYNC=1, the `sync=1` step) whose workgroups each take a key split, wait for the
+    head's partials and merge them; and the default past NXD_DECODE_ATTN_OPROJ_MAXL, the split attention
+    launch whose partials the o_proj launch merges (`l2`) -- one decode step each against the split
     attention + merge + o_proj launches on identical caches."""
     from transformers import LlamaConfig, LlamaForCausalLM as HF
     from neuronx_distributed_llama3_2_amd.inference import model_base
