@@ -69,6 +69,8 @@ int mx_expert_gemv_launch(const void*, int64_t, int64_t, const void*, int64_t, i
                           const int32_t*, int, int, int, void*, int64_t, int64_t, int, int, int, int, hipStream_t);
 int mx_mfma_launch(const void*, int64_t, int64_t, const void*, int64_t, int64_t, const void*, int64_t, int64_t, const void*,
                    int, void*, int64_t, int64_t, int, int, int, int, int, hipStream_t);
+int mx_wide_launch(const void*, int64_t, const void*, int64_t, const void*, int64_t, const void*, void*, int64_t, int, int,
+                   int, int, int, hipStream_t);
 int expert_gemv_launch(const void*, int64_t, const void*, int64_t, int64_t, const int32_t*, int, int, void*, int64_t, int,
                        int, int, hipStream_t);
 void dgemv_set_knob(int, int);
@@ -995,6 +997,37 @@ void mx_gemm(at::Tensor x, at::Tensor w, at::Tensor scale, c10::optional<at::Ten
            "mx_gemm");
 }
 
+// mx_gemm for 1 <= M <= 512 rows (csrc/gemm_mx.hip: row chunks through LDS): the same operands and checks.  cfg = 0
+// lets the launcher pick the instantiation; tests and the benchmark tool force it with cfg = 256 MT + 16 T + KS.
+void mx_gemm_wide(at::Tensor x, at::Tensor w, at::Tensor scale, c10::optional<at::Tensor> bias, at::Tensor y, bool glu,
+                  int64_t cfg) {
+  check_cuda(x, "x");
+  check_bf16(x, "x");
+  check_bf16(y, "y");
+  check_cuda(y, "y");
+  TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && x.stride(1) == 1 && y.stride(1) == 1,
+              "mx_gemm_wide: 2-D x / y, unit inner strides");
+  const int64_t M = x.size(0), K = x.size(1), N = y.size(1);
+  check_mx(w, scale, K, "mx_gemm_wide");
+  TORCH_CHECK(M >= 1 && M <= 512 && y.size(0) == M, "mx_gemm_wide: 1 <= M <= 512");
+  TORCH_CHECK(N >= 1 && w.size(0) == (glu ? 2 * N : N), "mx_gemm_wide: weight shape mismatch");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && x.stride(0) >= K && y.stride(0) >= N &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "mx_gemm_wide: 16-byte aligned activation rows required");
+  TORCH_CHECK(w.stride(0) >= K / 2 && scale.stride(0) >= K / 32, "mx_gemm_wide: weight / scale rows must not overlap");
+  TORCH_CHECK(x.device() == w.device() && y.device() == w.device(), "mx_gemm_wide: operands on different devices");
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    check_bf16(*bias, "bias");
+    check_cuda(*bias, "bias");
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == w.size(0), "mx_gemm_wide: bias must be [Nw]");
+    bp = bias->data_ptr();
+  }
+  check_rc(nxd::mx_wide_launch(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), scale.data_ptr(), scale.stride(0), bp,
+                               y.data_ptr(), y.stride(0), (int)M, (int)N, (int)K, glu, (int)cfg, cur_stream()),
+           "mx_gemm_wide");
+}
+
 // mx_experts_gemv on MFMA weight tiles: every expert, 1 <= M <= 16 rows; x [M, K] (shared) or [E, M, K], y [E, M, N]
 void mx_experts_gemm(at::Tensor x, at::Tensor w, at::Tensor scale, at::Tensor y, bool glu, int64_t cfg) {
   check_cuda(x, "x");
@@ -1365,6 +1398,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("mx_gemv", &mx_gemv);
   m.def("mx_gemm", &mx_gemm, py::arg("x"), py::arg("w"), py::arg("scale"), py::arg("bias"), py::arg("y"), py::arg("glu"),
         py::arg("cfg") = 0);
+  m.def("mx_gemm_wide", &mx_gemm_wide, py::arg("x"), py::arg("w"), py::arg("scale"), py::arg("bias"), py::arg("y"),
+        py::arg("glu"), py::arg("cfg") = 0);
   m.def("mx_experts_gemm", &mx_experts_gemm, py::arg("x"), py::arg("w"), py::arg("scale"), py::arg("y"), py::arg("glu"),
         py::arg("cfg") = 0);
   m.def("mx_dequant", &mx_dequant);

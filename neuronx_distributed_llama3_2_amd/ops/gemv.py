@@ -219,12 +219,27 @@ def mx_route(M: int) -> str:
     return "gemv" if 1 <= M <= 8 else "dequant"
 
 
+# NXD_MX_WIDE: the largest row count M up to which mx_linear, above the MX_GEMM_MAX_ROWS rows of mx_route,
+# reads the 4-bit weights directly (mx_gemm_wide, csrc/gemm_mx.hip, at most MX_WIDE_MAX_ROWS rows) instead of
+# dequantising the weight and calling the GEMM; 0 = never, which is the route before this kernel.  Read
+# once per process.  The default is justified in the README (Measured performance, MXFP4 at 17-512 rows).
+MX_WIDE_MAX_ROWS = 512
+_MX_WIDE_DEFAULT = 0
+_MX_WIDE = int(os.environ.get("NXD_MX_WIDE", str(_MX_WIDE_DEFAULT)))
+
+
+def mx_wide_ok(M: int) -> bool:
+    """Whether an M-row MXFP4 product that mx_route sends to "dequant" takes mx_gemm_wide instead."""
+    return MX_GEMM_MAX_ROWS < M <= min(_MX_WIDE, MX_WIDE_MAX_ROWS)
+
+
 def mx_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None,
               glu: bool = False) -> torch.Tensor:
     """x [..., K] @ deq(W)^T (+ bias) for MXFP4 W (packed [Nw, K/2], scale [Nw, K/32]); glu=True:
     W = [gate; up] rows and the result is silu(gate) * up of width Nw / 2.  Decode-sized bf16 inputs
-    on the GPU (M <= 16) read the 4-bit weights directly (mx_gemv or mx_gemm, see mx_route);
-    everything else dequantises and goes through the GEMM."""
+    on the GPU (M <= 16) read the 4-bit weights directly (mx_gemv or mx_gemm, see mx_route), and so
+    do up to NXD_MX_WIDE rows (mx_gemm_wide, see mx_wide_ok); everything else dequantises and goes
+    through the GEMM."""
     _check_mxfp4(packed, scale)
     K = x.shape[-1]
     if packed.dim() != 2 or packed.shape[1] * 2 != K:
@@ -234,13 +249,15 @@ def mx_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, bias: 
     Nw = packed.shape[0]
     N = Nw // 2 if glu else Nw
     route = mx_route(M)
+    if route == "dequant" and mx_wide_ok(M):
+        route = "wide"
     if use_native(x, packed, scale) and route != "dequant" and x.dtype == torch.bfloat16 and N >= 1 and \
             _mx_native_ok(packed, scale) and (bias is None or bias.dtype == torch.bfloat16):
         x2 = x.reshape(M, K)
         if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.data_ptr() % 16:
             x2 = x2.contiguous()
         y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-        kernel = ext().mx_gemm if route == "gemm" else ext().mx_gemv
+        kernel = getattr(ext(), {"gemm": "mx_gemm", "gemv": "mx_gemv", "wide": "mx_gemm_wide"}[route])
         kernel(x2, packed, scale, bias.contiguous() if bias is not None else None, y, glu)
         return y.view(lead + (N,))
     y = _linear(x, dequantize_mxfp4(packed, scale, x.dtype), bias)

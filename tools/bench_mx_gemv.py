@@ -1,8 +1,10 @@
 """Decode projection A/B on one MI355X: MXFP4 weights on the VALU kernel (mx_gemv, csrc/gemv_mx.hip;
 above its 8 rows mx_dequant + GEMM, the route without an MFMA form) and on MFMA weight tiles
 (mx_gemm, csrc/gemv_mx_mfma.hip) against skinny_linear with int8 and with bf16 weights
-(csrc/gemv.hip) on Llama-3.2-1B / Llama-3-8B projection shapes at 1..16 activation rows.  The two
-MXFP4 kernels are called directly, so the result does not depend on the routing knob NXD_MX_MFMA.
+(csrc/gemv.hip) on Llama-3.2-1B / Llama-3-8B projection shapes at 1..16 activation rows, and up to
+512 rows the row-chunk kernel (mxfp4_wide: mx_gemm_wide, csrc/gemm_mx.hip) against dequant + GEMM
+(mxfp4) and the bf16 GEMM.  The MXFP4 kernels are called directly, so the result does not depend on
+the routing knobs NXD_MX_MFMA / NXD_MX_WIDE.
 
 The four variants alternate in one process.  Each is a captured hipGraph of calls that rotate over
 enough weight copies to exceed the 256 MiB Infinity Cache, so every call streams its weights from
@@ -52,6 +54,7 @@ def make_weights(kind, Nw, K, copies):
 
 
 MFMA_CFG = 0   # --cfg: force tiles per wave / K split of mx_gemm (16 T + KS), 0 = the launcher's choice
+WIDE_CFG = 0   # --wide-cfg: force mx_gemm_wide's instantiation (256 MT + 16 T + KS), 0 = the launcher's choice
 
 
 def call(kind, x, w, glu):
@@ -63,6 +66,8 @@ def call(kind, x, w, glu):
         y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
         if kind == "mxfp4":
             ext().mx_gemv(x, w[0], w[1], None, y, glu)
+        elif kind == "mxfp4_wide":
+            ext().mx_gemm_wide(x, w[0], w[1], None, y, glu, WIDE_CFG)
         else:
             ext().mx_gemm(x, w[0], w[1], None, y, glu, MFMA_CFG)
         return y
@@ -100,15 +105,17 @@ def main():
     ap.add_argument("--only", default=None, help="model name filter")
     ap.add_argument("--kinds", default="mxfp4,mxfp4_mfma,int8,bf16")
     ap.add_argument("--cfg", type=int, default=0, help="force mx_gemm's tiles per wave T and K split KS: 16 T + KS")
+    ap.add_argument("--wide-cfg", type=int, default=0,
+                    help="force mx_gemm_wide's row tiles MT, tiles per wave T and K split KS: 256 MT + 16 T + KS")
     a = ap.parse_args()
-    global MFMA_CFG
-    MFMA_CFG = a.cfg
+    global MFMA_CFG, WIDE_CFG
+    MFMA_CFG, WIDE_CFG = a.cfg, a.wide_cfg
     if not torch.cuda.is_available():
         raise SystemExit("bench_mx_gemv needs a GPU")
     sink = open(a.out, "a") if a.out else None
     kinds = tuple(a.kinds.split(","))
-    if any(not 1 <= int(m) <= 16 for m in a.rows.split(",")):
-        raise SystemExit("--rows: 1..16")
+    if any(not 1 <= int(m) <= 512 for m in a.rows.split(",")):
+        raise SystemExit("--rows: 1..512")
     for model, op, K, Nw, glu in SHAPES:
         if a.only and a.only != model:
             continue
@@ -118,6 +125,7 @@ def main():
             weights[kind] = make_weights(kind, Nw, K, copies)
         for M in (int(m) for m in a.rows.split(",")):
             x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
+            all_kinds, kinds = kinds, tuple(k for k in kinds if not (k == "mxfp4_mfma" and M > 16))
             inner = {k: 4 * len(weights[k]) for k in kinds}
             graphs = {k: capture(k, x, weights[k], glu, inner[k]) for k in kinds}
             # replays sized for a window of about 30 ms per sample
@@ -135,12 +143,15 @@ def main():
                        "copies": len(weights[k])}
                 if k == "mxfp4_mfma" and a.cfg:
                     rec["cfg"] = a.cfg
+                if k == "mxfp4_wide" and a.wide_cfg:
+                    rec["cfg"] = a.wide_cfg
                 line = json.dumps(rec)
                 print(line, flush=True)
                 if sink:
                     sink.write(line + "\n")
                     sink.flush()
             del graphs
+            kinds = all_kinds
         del weights
         torch.cuda.empty_cache()
     if sink:
