@@ -77,6 +77,8 @@ void dgemv_set_knob(int, int);
 int dgemv_launch(int, const void*, int64_t, const void*, float, const void*, int64_t, void*, int64_t, int, int, int, int,
                  int, int, const float*, const float*, const int64_t*, int, void*, void*, int64_t, int64_t, int64_t,
                  const int*, int, int, const float*, float*, hipStream_t, const int64_t*, int64_t, void*, float*);
+int dgemv_mx_launch(int, const void*, int64_t, const void*, float, const void*, int64_t, const void*, int64_t, void*, int64_t,
+                    int, int, int, int, hipStream_t);
 int grouped_gemm_launch(int, const void*, const void*, void*, const int*, int, int, int, int, hipStream_t);
 int wgrad_gemm_launch(const void*, int64_t, const void*, int64_t, float*, int64_t, int, int, int, int, hipStream_t);
 int wgrad_gemm_choose_splits(int, int, int);
@@ -1347,6 +1349,41 @@ void dgemv(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, double e
            "dgemv");
 }
 
+// Fused decode GEMV over MXFP4 weights (csrc/decode_fused_mx.hip).  epi: 0 plain, 1 residual add into y (in place),
+// 2 SwiGLU on a fused [2N, K] gate/up weight; 0 and 2 take the RMSNorm of x as a prologue (norm_w required), 1 takes
+// none.  x [M, K] bf16 with M <= 3, w / scale as mx_gemv, y [M, N] bf16, no bias.  cfg = 0 lets the launcher pick
+// rows per wave R and k-slices KS; tests and the benchmark tool force them with cfg = 16 R + KS.
+void dgemv_mx(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, double eps, at::Tensor w, at::Tensor scale,
+              at::Tensor y, int64_t cfg) {
+  check_bf16(x, "x");
+  check_bf16(y, "y");
+  TORCH_CHECK(epi >= 0 && epi <= 2, "dgemv_mx: epi must be 0..2");
+  TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && x.stride(1) == 1 && y.stride(1) == 1, "dgemv_mx: 2-D x / y, unit inner strides");
+  const int64_t M = x.size(0), K = x.size(1), N = y.size(1);
+  check_mx(w, scale, K, "dgemv_mx");
+  TORCH_CHECK(M >= 1 && M <= 3 && y.size(0) == M, "dgemv_mx: 1 <= M <= 3");
+  TORCH_CHECK(N >= 1 && w.size(0) == (epi == 2 ? 2 * N : N), "dgemv_mx: weight shape mismatch");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && x.stride(0) >= K && y.stride(0) >= N &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "dgemv_mx: 16-byte aligned activation rows required");
+  TORCH_CHECK(w.stride(0) >= K / 2 && scale.stride(0) >= K / 32, "dgemv_mx: weight / scale rows must not overlap");
+  TORCH_CHECK(x.device() == w.device() && y.device() == w.device(), "dgemv_mx: operands on different devices");
+  TORCH_CHECK(norm_w.has_value() == (epi != 1), "dgemv_mx: epi 0 / 2 need the norm weight, epi 1 takes none");
+  const void* nw = nullptr;
+  if (norm_w.has_value()) {
+    check_bf16(*norm_w, "norm_w");
+    TORCH_CHECK(norm_w->is_contiguous() && norm_w->numel() == K && norm_w->device() == w.device(), "dgemv_mx: norm weight [K]");
+    check_aligned16(*norm_w, "norm_w");
+    TORCH_CHECK(M * K * 2 <= 65536, "dgemv_mx: fused norm needs M * K <= 32768");
+    nw = norm_w->data_ptr();
+  }
+  TORCH_CHECK(cfg == 0 || (cfg >= 17 && cfg <= 68), "dgemv_mx: cfg = 16 R + KS");
+  check_rc(nxd::dgemv_mx_launch((int)epi, x.data_ptr(), x.stride(0), nw, (float)eps, w.data_ptr(), w.stride(0),
+                                scale.data_ptr(), scale.stride(0), y.data_ptr(), y.stride(0), (int)M, (int)N, (int)K, (int)cfg,
+                                cur_stream()),
+           "dgemv_mx");
+}
+
 }  // namespace
 
 void register_gemm(pybind11::module& m);  // gemm.cpp
@@ -1450,6 +1487,8 @@ PYBIND11_MODULE(_C, m) {
         py::arg("nq"), py::arg("nkv"), py::arg("D"), py::arg("cos_t"), py::arg("sin_t"), py::arg("pos"), py::arg("T"),
         py::arg("kc"), py::arg("vc"), py::arg("cache_idx"), py::arg("xadd") = py::none(), py::arg("yadd") = py::none(),
         py::arg("xidx") = py::none(), py::arg("xcopy") = py::none());
+  m.def("dgemv_mx", &dgemv_mx, py::arg("epi"), py::arg("x"), py::arg("norm_w"), py::arg("eps"), py::arg("w"), py::arg("scale"),
+        py::arg("y"), py::arg("cfg") = 0);
   // decode A/B knobs: 0 = GLU row pairs per wave, 1 = GEMV k-slices (0 auto), 2 = MFMA decode attention on/off,
   // 3 = GEMV early epilogue / prologue reads on/off, 5 = bs = 1 GEMV forced occupancy (0 natural | 7 | 8 waves / SIMD)
   m.def("decode_set_knob", [](int which, int value) {

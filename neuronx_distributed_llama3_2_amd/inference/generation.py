@@ -309,6 +309,7 @@ class LlamaForCausalLMInference:
         the one-shot peer all-reduce) against the unfused per-op decode; the next decode step re-checks
         whether the model can take the fused path."""
         self.model._decode_fused_ok = None if enabled else False
+        self.model._decode_fused_mx_ok = None if enabled else False   # the MXFP4 form of the same launches
 
     def _context_encode(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                         position_ids: Optional[torch.Tensor] = None, seq_ids: Optional[torch.Tensor] = None) -> torch.Tensor:

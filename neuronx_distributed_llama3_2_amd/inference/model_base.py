@@ -35,7 +35,7 @@ import torch.distributed as dist
 
 from .. import ops
 from ..ops.gemm import linear as _linear
-from ..ops.gemv import mx_linear, skinny_linear
+from ..ops.gemv import MX_DECODE_MAX_ROWS, _mx_native_ok, mx_linear, mx_route, skinny_linear
 from ..parallel_layers import parallel_state as ps
 from ..parallel_layers.parallel_state import get_tensor_model_parallel_size
 
@@ -59,6 +59,11 @@ _ATTN_OPROJ_MAXB = int(os.environ.get("NXD_DECODE_ATTN_OPROJ_MAXB", "2"))
 # embedding row of each token id and workgroup 0 writes it to the residual stream): one launch less
 # per decode step.  NXD_DECODE_EMB_FUSED=0 keeps the separate embedding kernel (A/B).
 _EMB_FUSED = os.environ.get("NXD_DECODE_EMB_FUSED", "1") == "1"
+# NXD_DECODE_FUSED_MX: a weight-quantized (MXFP4) Llama decodes at 1-3 rows on the fused launches of
+# csrc/decode_fused_mx.hip instead of the ten per-op launches per layer.  Read with NXD_DECODE_FUSED when
+# a model is first checked (_check_decode_fusable_mx).  The default is justified in the README
+# (Measured performance, fused MXFP4 decode).
+_FUSED_MX_DEFAULT = "1"
 
 
 class DecoderInferenceMixin:
@@ -98,6 +103,7 @@ class DecoderInferenceMixin:
             self.kv_cache_scale = torch.zeros(shape[:-1] + (self.head_dim // ops.decode.MX8_BLOCK,), dtype=torch.uint8,
                                               device=device) if quant else None
             self._decode_fused_ok = None   # the fused decode launches read and write a bf16 cache
+            self._decode_fused_mx_ok = None
         return self.kv_cache
 
     def reset_kv_cache(self) -> None:
@@ -160,6 +166,8 @@ class DecoderInferenceMixin:
         B, T = input_ids.shape
         if not prefill and self._decode_fusable(input_ids):
             return self._forward_decode_fused(input_ids, positions, seq_ids, cache_len, last_index, return_hidden)
+        if not prefill and self._decode_fusable_mx(input_ids):
+            return self._forward_decode_fused_mx(input_ids, positions, seq_ids, cache_len, last_index, return_hidden)
         nq, nkv, D = self.nq, self.nkv, self.head_dim
         W = (nq + 2 * nkv) * D
         cos_t, sin_t = self.model.rope_cache.tables(input_ids.device)
@@ -308,6 +316,104 @@ class DecoderInferenceMixin:
         logits = torch.empty((h2.shape[0], self.lm_head.weight.shape[0]), dtype=res.dtype, device=res.device)
         C.dgemv(0, h2, self.model.norm.weight, self.eps, self.lm_head.weight, logits, 0, 0, 0, None, None, None, 1,
                 None, None, None)                                       # final norm + lm_head
+        logits = logits.view(h.shape[:-1] + (logits.shape[-1],))
+        if return_hidden:
+            return logits, ops.rms_norm(h, self.model.norm.weight, self.eps)[0]
+        return logits
+
+    # ------------------------------------------------------------------ fused decode path, MXFP4 weights
+    def _fused_mx_ffn_weights(self, layer):
+        """(post-attention norm weight, gate_up module, down module) when the feed-forward block is a
+        dense bias-free SwiGLU MLP held in MXFP4 (uint8 `weight` + `scale`), else None."""
+        return None
+
+    @staticmethod
+    def _mx_packed(mod) -> bool:
+        w = getattr(mod, "weight", None)
+        s = getattr(mod, "scale", None)
+        return w is not None and s is not None and w.dtype == torch.uint8 and s.dtype == torch.uint8 and \
+            getattr(mod, "bias", None) is None and _mx_native_ok(w, s)
+
+    def _decode_fusable_mx(self, input_ids: torch.Tensor) -> bool:
+        ok = getattr(self, "_decode_fused_mx_ok", None)
+        if ok is None:
+            ok = self._check_decode_fusable_mx()
+            self._decode_fused_mx_ok = ok
+        M = input_ids.numel()
+        return ok and input_ids.is_cuda and M <= MX_DECODE_MAX_ROWS and mx_route(M) == "gemv" and \
+            M * self.config.hidden_size <= 32768
+
+    def _check_decode_fusable_mx(self) -> bool:
+        """Whether a weight-quantized model decodes on the fused launches that read MXFP4
+        (csrc/decode_fused_mx.hip): TP = 1, bf16 KV cache, bf16 bias-free QKV, every o_proj / gate_up /
+        down and the lm_head bias-free MXFP4.  NXD_DECODE_FUSED_MX (default: _FUSED_MX_DEFAULT) and
+        NXD_DECODE_FUSED=0 switch it off."""
+        if os.environ.get("NXD_DECODE_FUSED", "1") == "0" or \
+                os.environ.get("NXD_DECODE_FUSED_MX", _FUSED_MX_DEFAULT) == "0":
+            return False
+        if self.tp > 1 or self._kv_quantized():
+            return False
+        if type(self)._qkv_hook is not DecoderInferenceMixin._qkv_hook or type(self)._norm is not DecoderInferenceMixin._norm:
+            return False
+        if self.head_dim % 2 or self.head_dim > 256:
+            return False
+        for layer in self.model.layers:
+            attn = layer.self_attn
+            w, b = attn.qkv_proj._fused_weight_bias() if hasattr(attn.qkv_proj, "_fused_weight_bias") \
+                else (attn.qkv_proj.weight, getattr(attn.qkv_proj, "bias", None))
+            if b is not None or w.dtype != torch.bfloat16:
+                return False
+            if not self._mx_packed(attn.o_proj) or self._fused_mx_ffn_weights(layer) is None:
+                return False
+        return self._mx_packed(self.lm_head)
+
+    def _forward_decode_fused_mx(self, input_ids, positions, seq_ids, cache_len, last_index, return_hidden):
+        """_forward_decode_fused for MXFP4 projections: per layer dgemv(QKV + RoPE + cache write, bf16),
+        decode attention, dgemv_mx(o_proj + residual), dgemv_mx(norm + gate_up + SwiGLU),
+        dgemv_mx(down + residual); then dgemv_mx(final norm + lm_head).  Static shapes, no host sync."""
+        C = ops.ext()
+        B, T = input_ids.shape
+        M = B * T
+        nq, nkv, D = self.nq, self.nkv, self.head_dim
+        W = (nq + 2 * nkv) * D
+        cos_t, sin_t = self.model.rope_cache.tables(input_ids.device)
+        pos = positions.reshape(-1).to(torch.int64).contiguous()
+        sid32 = seq_ids.to(torch.int32).contiguous() if seq_ids is not None else None
+        emb = self.model.embed_tokens
+        ew = emb.weight
+        emb_fused = (_EMB_FUSED and emb.start_index == 0 and ew.dtype == torch.bfloat16 and ew.is_contiguous()
+                     and input_ids.dtype == torch.int64)
+        if emb_fused:
+            ids = input_ids.reshape(-1).contiguous()
+            res = torch.empty((M, ew.shape[1]), dtype=ew.dtype, device=ew.device)   # written by layer 0's QKV
+        else:
+            res = ops.vocab_parallel_embedding(input_ids, ew, emb.start_index).reshape(M, -1).contiguous()
+        qkv = torch.empty((M, W), dtype=res.dtype, device=res.device)
+        window = self._decode_window()
+        for i, layer in enumerate(self.model.layers):
+            attn = layer.self_attn
+            w_qkv = attn.qkv_proj._fused_weight_bias()[0] if hasattr(attn.qkv_proj, "_fused_weight_bias") \
+                else attn.qkv_proj.weight
+            kc, vc = self.kv_cache[i, 0], self.kv_cache[i, 1]
+            if i == 0 and emb_fused:
+                C.dgemv(3, ew, layer.input_layernorm.weight, self.eps, w_qkv, qkv, nq, nkv, D, cos_t, sin_t, pos, T,
+                        kc, vc, sid32, xidx=ids, xcopy=res)
+            else:
+                C.dgemv(3, res, layer.input_layernorm.weight, self.eps, w_qkv, qkv, nq, nkv, D, cos_t, sin_t, pos, T,
+                        kc, vc, sid32)
+            q = qkv.view(B, T, nq + 2 * nkv, D)[:, :, :nq]
+            ln2, gu, dn = self._fused_mx_ffn_weights(layer)
+            o = ops.decode_attention(q, kc, vc, cache_len, sid32, window=window)
+            C.dgemv_mx(1, o.reshape(M, nq * D), None, 0.0, attn.o_proj.weight, attn.o_proj.scale, res)   # res += o_proj(o)
+            a = torch.empty((M, gu.weight.shape[0] // 2), dtype=res.dtype, device=res.device)
+            C.dgemv_mx(2, res, ln2, self.eps, gu.weight, gu.scale, a)                                 # norm + SwiGLU
+            C.dgemv_mx(1, a, None, 0.0, dn.weight, dn.scale, res)                                     # res += down(a)
+        h = res.view(B, T, -1)
+        if last_index is not None:
+            h = h[torch.arange(B, device=h.device), last_index]
+        h2 = h.reshape(-1, h.shape[-1]).contiguous()
+        logits = torch.empty((h2.shape[0], self.lm_head.weight.shape[0]), dtype=res.dtype, device=res.device)
+        C.dgemv_mx(0, h2, self.model.norm.weight, self.eps, self.lm_head.weight, self.lm_head.scale, logits)
         logits = logits.view(h.shape[:-1] + (logits.shape[-1],))
         if return_hidden:
             return logits, ops.rms_norm(h, self.model.norm.weight, self.eps)[0]

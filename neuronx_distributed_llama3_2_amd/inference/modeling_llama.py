@@ -32,6 +32,13 @@ class LlamaInferenceModel(DecoderInferenceMixin, LlamaForCausalLM):
             return None
         return layer.post_attention_layernorm.weight, w_gu, w_d
 
+    def _fused_mx_ffn_weights(self, layer):
+        mlp = layer.mlp
+        if not (self._mx_packed(mlp.gate_up_proj) and self._mx_packed(mlp.down_proj)) or \
+                mlp.gate_up_proj.weight.shape[0] % 2:
+            return None
+        return layer.post_attention_layernorm.weight, mlp.gate_up_proj, mlp.down_proj
+
     def _ffn(self, layer, h: torch.Tensor) -> torch.Tensor:
         mlp = layer.mlp
         a = self._proj(mlp.gate_up_proj, h, glu=True)   # SwiGLU fused into the decode GEMV

@@ -268,6 +268,66 @@ def mx_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, bias: 
     return y
 
 
+MX_DECODE_MAX_ROWS = 3
+
+
+def mx_decode_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, *,
+                     norm_weight: Optional[torch.Tensor] = None, eps: float = 0.0, glu: bool = False,
+                     residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A decode projection over MXFP4 W with the element-wise work around it, in the three forms of
+    csrc/decode_fused_mx.hip (rounding points: tests/decode_refs.py with w the dequantized weight):
+
+    * norm_weight:            bf16(RMSNorm(x) @ deq(W)^T)                  (final norm + lm_head)
+    * norm_weight, glu=True:  bf16(silu(g) * u) of RMSNorm(x) @ deq([gate; up])^T   (gate_up)
+    * residual:               residual <- bf16(residual + bf16(x @ deq(W)^T)), in place; returns it
+                              (o_proj, down)
+
+    One launch each for at most MX_DECODE_MAX_ROWS bf16 rows on the GPU while mx_route keeps those rows
+    on the VALU kernel; every other case (and every other combination of the arguments) composes
+    ops.rms_norm, mx_linear and the add."""
+    _check_mxfp4(packed, scale)
+    K = x.shape[-1]
+    if packed.dim() != 2 or packed.shape[1] * 2 != K:
+        raise ValueError(f"mx_decode_linear: x [..., {K}] against packed weight {tuple(packed.shape)}")
+    if glu and residual is not None:
+        raise ValueError("mx_decode_linear: glu and residual do not combine")
+    lead = x.shape[:-1]
+    M = x.numel() // K
+    Nw = packed.shape[0]
+    N = Nw // 2 if glu else Nw
+    if residual is not None and (residual.shape[-1] != N or residual.numel() != M * N):
+        raise ValueError(f"mx_decode_linear: residual {tuple(residual.shape)} against {M} rows of {N}")
+    fused_form = (norm_weight is not None) != (residual is not None)   # a prologue or an epilogue, not both
+    if fused_form and use_native(x, packed, scale) and 1 <= M <= MX_DECODE_MAX_ROWS and mx_route(M) == "gemv" and \
+            x.dtype == torch.bfloat16 and N >= 1 and _mx_native_ok(packed, scale) and \
+            (Nw % 2 == 0 or not glu) and packed.stride(0) >= K // 2 and scale.stride(0) >= K // MX_BLOCK:
+        y = None
+        if residual is None:
+            nw = norm_weight.contiguous()
+            if nw.dtype == torch.bfloat16 and nw.numel() == K and nw.data_ptr() % 16 == 0 and M * K <= 32768:
+                y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+        elif residual.dtype == torch.bfloat16 and residual.device == x.device and residual.stride(-1) == 1 and \
+                (residual.is_contiguous() or (residual.dim() == 2 and residual.stride(0) >= N)):
+            nw = None
+            y = residual if residual.dim() == 2 else residual.view(M, N)
+        if y is not None:
+            x2 = x.reshape(M, K)
+            if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.stride(0) < K or x2.data_ptr() % 16:
+                x2 = x2.contiguous()
+            ext().dgemv_mx(1 if residual is not None else (2 if glu else 0), x2, nw, float(eps), packed, scale, y)
+            return residual if residual is not None else y.view(lead + (N,))
+    h = x
+    if norm_weight is not None:
+        from .norm import rms_norm
+
+        h = rms_norm(x, norm_weight, eps)[0]
+    y = mx_linear(h, packed, scale, None, glu=glu)
+    if residual is None:
+        return y
+    residual.add_(y.reshape(residual.shape))
+    return residual
+
+
 def _check_mx_stack(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, glu: bool, op: str) -> None:
     _check_mxfp4(packed, scale)
     if packed.dim() != 3 or packed.shape[2] * 2 != x.shape[-1]:

@@ -1,0 +1,150 @@
+"""Fused decode launches over MXFP4 weights (dgemv_mx, csrc/decode_fused_mx.hip) on one MI355X against what each
+replaces and against the bf16 fused launch of the same shape, on the Llama-3.2-1B / Llama-3-8B decode projections
+at 1-3 activation rows:
+
+  fused     one dgemv_mx launch: o_proj / down with the residual add, gate_up with RMSNorm + SwiGLU, norm + lm_head
+  unfused   the launches it replaces: rms_norm + mx_gemv (gate_up, lm_head), mx_gemv + add (o_proj, down)
+  bf16      dgemv (csrc/decode_fused.hip) with bf16 weights, same epilogue and prologue
+
+The kernels are called directly, so the result does not depend on NXD_DECODE_FUSED_MX.  The variants alternate in
+one process; each is a captured hipGraph of calls that rotate over more than 512 MiB of weight copies (the Infinity
+Cache holds 256 MiB), so every call streams its weights from HBM.  One JSON line per (shape, rows, variant): median
+time per call over the rounds, its min / max (the run-to-run spread), the bytes the call must move (weights,
+scales, activations in and out) and the rate that gives."""
+import argparse
+import json
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, ".")
+from neuronx_distributed_llama3_2_amd.ops import ext, rms_norm  # noqa: E402
+
+PLAIN, RESID, GLU = 0, 1, 2
+MODELS = {"llama3.2-1b": (2048, 8192, 128256), "llama3-8b": (4096, 14336, 128256)}   # hidden, intermediate, vocabulary
+ROTATE_BYTES = 512 << 20
+EPS = 1e-5
+CFG = 0   # --cfg: force dgemv_mx's rows per wave R and k-slices KS (16 R + KS); 0 = the launcher's choice
+
+
+def shapes(model):
+    H, I, V = MODELS[model]   # op, epilogue, K, weight rows
+    return [("o_proj", RESID, H, H), ("gate_up", GLU, H, 2 * I), ("down", RESID, I, H), ("lm_head", PLAIN, H, V)]
+
+
+def weight_bytes(kind, Nw, K):
+    return Nw * K * 2 if kind == "bf16" else Nw * K // 2 + Nw * K // 32
+
+
+def make_weights(kind, Nw, K, copies):
+    if kind == "bf16":
+        return [(torch.randn(Nw, K, device="cuda", dtype=torch.bfloat16) * 0.02,) for _ in range(copies)]
+    return [(torch.randint(0, 256, (Nw, K // 2), device="cuda", dtype=torch.uint8),
+             torch.randint(120, 128, (Nw, K // 32), device="cuda", dtype=torch.uint8)) for _ in range(copies)]
+
+
+def call(kind, epi, x, nw, w, res):
+    """One projection; res is the [M, N] residual stream of the RESID forms (updated in place)."""
+    C = ext()
+    M, N = x.shape[0], w[0].shape[0] // (2 if epi == GLU else 1)
+    y = res if epi == RESID else torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    norm = None if epi == RESID else nw
+    if kind == "fused":
+        C.dgemv_mx(epi, x, norm, EPS, w[0], w[1], y, CFG)
+    elif kind == "bf16":
+        C.dgemv(epi, x, norm, EPS, w[0], y, 0, 0, 0, None, None, None, 1, None, None, None)
+    elif epi == RESID:
+        t = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+        C.mx_gemv(x, w[0], w[1], None, t, False)
+        res.add_(t)
+    else:
+        C.mx_gemv(rms_norm(x, nw, EPS)[0], w[0], w[1], None, y, epi == GLU)
+    return y
+
+
+def capture(kind, epi, x, nw, ws, res, inner):
+    for w in ws:   # warm every buffer the graph uses
+        call(kind, epi, x, nw, w, res)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for i in range(inner):
+            call(kind, epi, x, nw, ws[i % len(ws)], res)
+    g.replay()
+    torch.cuda.synchronize()
+    return g
+
+
+def time_graph(g, replays):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(replays):
+        g.replay()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) * 1000.0 / replays   # us per replay
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--rows", default="1,2,3")
+    ap.add_argument("--only", default=None, help="model name filter")
+    ap.add_argument("--ops", default=None, help="comma-separated projection filter (o_proj,gate_up,down,lm_head)")
+    ap.add_argument("--kinds", default="fused,unfused,bf16")
+    ap.add_argument("--cfg", type=int, default=0, help="force dgemv_mx's rows per wave R and k-slices KS: 16 R + KS")
+    a = ap.parse_args()
+    global CFG
+    CFG = a.cfg
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_mx_decode needs a GPU")
+    rows = [int(m) for m in a.rows.split(",")]
+    if any(not 1 <= m <= 3 for m in rows):
+        raise SystemExit("--rows: 1..3")
+    kinds = tuple(a.kinds.split(","))
+    sink = open(a.out, "a") if a.out else None
+    for model in MODELS:
+        if a.only and a.only != model:
+            continue
+        for op, epi, K, Nw in shapes(model):
+            if a.ops and op not in a.ops.split(","):
+                continue
+            N = Nw // 2 if epi == GLU else Nw
+            weights = {k: make_weights(k, Nw, K, max(2, -(-ROTATE_BYTES // weight_bytes(k, Nw, K)))) for k in kinds}
+            nw = torch.ones(K, device="cuda", dtype=torch.bfloat16)
+            for M in rows:
+                x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
+                res = torch.zeros(M, N, device="cuda", dtype=torch.bfloat16)
+                inner = {k: 4 * len(weights[k]) for k in kinds}
+                graphs = {k: capture(k, epi, x, nw, weights[k], res, inner[k]) for k in kinds}
+                # replays sized for a window of about 30 ms per sample
+                reps = {k: max(3, int(30000.0 / max(time_graph(graphs[k], 3), 1.0))) for k in kinds}
+                samples = {k: [] for k in kinds}
+                for _ in range(a.rounds):
+                    for k in kinds:   # alternate the variants
+                        samples[k].append(time_graph(graphs[k], reps[k]) / inner[k])
+                for k in kinds:
+                    us = statistics.median(samples[k])
+                    # what the call must move: weights (+ scales), x, the norm weight, y (RESID: read and written)
+                    nbytes = weight_bytes(k, Nw, K) + 2 * (M * K + (0 if epi == RESID else K) + M * N * (2 if epi == RESID else 1))
+                    rec = {"model": model, "op": op, "K": K, "Nw": Nw, "M": M, "variant": k, "us": round(us, 2),
+                           "us_min": round(min(samples[k]), 2), "us_max": round(max(samples[k]), 2), "bytes": nbytes,
+                           "TBps": round(nbytes / us / 1e6, 3), "rounds": a.rounds, "copies": len(weights[k])}
+                    if k == "fused" and a.cfg:
+                        rec["cfg"] = a.cfg
+                    line = json.dumps(rec)
+                    print(line, flush=True)
+                    if sink:
+                        sink.write(line + "\n")
+                        sink.flush()
+                del graphs
+            del weights
+            torch.cuda.empty_cache()
+    if sink:
+        sink.close()
+
+
+if __name__ == "__main__":
+    main()
