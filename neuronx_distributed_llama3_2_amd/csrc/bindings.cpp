@@ -77,6 +77,8 @@ void dgemv_set_knob(int, int);
 int dgemv_launch(int, const void*, int64_t, const void*, float, const void*, int64_t, void*, int64_t, int, int, int, int,
                  int, int, const float*, const float*, const int64_t*, int, void*, void*, int64_t, int64_t, int64_t,
                  const int*, int, int, const float*, float*, hipStream_t, const int64_t*, int64_t, void*, float*);
+int dgemv_mx_mfma_launch(int, const void*, int64_t, const void*, float, const void*, int64_t, const void*, int64_t, void*,
+                         int64_t, int, int, int, int, hipStream_t);
 int dgemv_mx_launch(int, const void*, int64_t, const void*, float, const void*, int64_t, const void*, int64_t, void*, int64_t,
                     int, int, int, int, hipStream_t);
 int grouped_gemm_launch(int, const void*, const void*, void*, const int*, int, int, int, int, hipStream_t);
@@ -1349,10 +1351,12 @@ void dgemv(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, double e
            "dgemv");
 }
 
-// Fused decode GEMV over MXFP4 weights (csrc/decode_fused_mx.hip).  epi: 0 plain, 1 residual add into y (in place),
-// 2 SwiGLU on a fused [2N, K] gate/up weight; 0 and 2 take the RMSNorm of x as a prologue (norm_w required), 1 takes
-// none.  x [M, K] bf16 with M <= 3, w / scale as mx_gemv, y [M, N] bf16, no bias.  cfg = 0 lets the launcher pick
-// rows per wave R and k-slices KS; tests and the benchmark tool force them with cfg = 16 R + KS.
+// Fused decode GEMV over MXFP4 weights.  epi: 0 plain, 1 residual add into y (in place), 2 SwiGLU on a fused [2N, K]
+// gate/up weight; 0 and 2 take the RMSNorm of x as a prologue (norm_w required), 1 takes none.  x [M, K] bf16,
+// w / scale as mx_gemv, y [M, N] bf16, no bias.  M <= 3 is the VALU kernel (csrc/decode_fused_mx.hip): cfg = 0 lets the
+// launcher pick rows per wave R and k-slices KS; tests and the benchmark tool force them with cfg = 16 R + KS.
+// 4 <= M <= 16 is the kernel on MFMA weight tiles (csrc/decode_fused_mx_mfma.hip), where cfg = 16 T + KS forces the
+// tiles per wave T and the k-slices KS, and the fused norm has no M * K limit.
 void dgemv_mx(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, double eps, at::Tensor w, at::Tensor scale,
               at::Tensor y, int64_t cfg) {
   check_bf16(x, "x");
@@ -1361,7 +1365,7 @@ void dgemv_mx(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, doubl
   TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && x.stride(1) == 1 && y.stride(1) == 1, "dgemv_mx: 2-D x / y, unit inner strides");
   const int64_t M = x.size(0), K = x.size(1), N = y.size(1);
   check_mx(w, scale, K, "dgemv_mx");
-  TORCH_CHECK(M >= 1 && M <= 3 && y.size(0) == M, "dgemv_mx: 1 <= M <= 3");
+  TORCH_CHECK(M >= 1 && M <= 16 && y.size(0) == M, "dgemv_mx: 1 <= M <= 16");
   TORCH_CHECK(N >= 1 && w.size(0) == (epi == 2 ? 2 * N : N), "dgemv_mx: weight shape mismatch");
   TORCH_CHECK(x.stride(0) % 8 == 0 && x.stride(0) >= K && y.stride(0) >= N &&
                   reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
@@ -1374,14 +1378,21 @@ void dgemv_mx(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, doubl
     check_bf16(*norm_w, "norm_w");
     TORCH_CHECK(norm_w->is_contiguous() && norm_w->numel() == K && norm_w->device() == w.device(), "dgemv_mx: norm weight [K]");
     check_aligned16(*norm_w, "norm_w");
-    TORCH_CHECK(M * K * 2 <= 65536, "dgemv_mx: fused norm needs M * K <= 32768");
+    TORCH_CHECK(M > 3 || M * K * 2 <= 65536, "dgemv_mx: fused norm at 1-3 rows needs M * K <= 32768");
     nw = norm_w->data_ptr();
   }
-  TORCH_CHECK(cfg == 0 || (cfg >= 17 && cfg <= 68), "dgemv_mx: cfg = 16 R + KS");
-  check_rc(nxd::dgemv_mx_launch((int)epi, x.data_ptr(), x.stride(0), nw, (float)eps, w.data_ptr(), w.stride(0),
-                                scale.data_ptr(), scale.stride(0), y.data_ptr(), y.stride(0), (int)M, (int)N, (int)K, (int)cfg,
-                                cur_stream()),
-           "dgemv_mx");
+  TORCH_CHECK(cfg == 0 || (cfg >= 17 && cfg <= 68), "dgemv_mx: cfg = 16 R + KS (4-16 rows: 16 T + KS)");
+  int rc;
+  if (M > 3) {   // MFMA weight tiles (csrc/decode_fused_mx_mfma.hip)
+    rc = nxd::dgemv_mx_mfma_launch((int)epi, x.data_ptr(), x.stride(0), nw, (float)eps, w.data_ptr(), w.stride(0),
+                                   scale.data_ptr(), scale.stride(0), y.data_ptr(), y.stride(0), (int)M, (int)N, (int)K,
+                                   (int)cfg, cur_stream());
+  } else {
+    rc = nxd::dgemv_mx_launch((int)epi, x.data_ptr(), x.stride(0), nw, (float)eps, w.data_ptr(), w.stride(0),
+                              scale.data_ptr(), scale.stride(0), y.data_ptr(), y.stride(0), (int)M, (int)N, (int)K, (int)cfg,
+                              cur_stream());
+  }
+  check_rc(rc, "dgemv_mx");
 }
 
 }  // namespace

@@ -35,7 +35,8 @@ import torch.distributed as dist
 
 from .. import ops
 from ..ops.gemm import linear as _linear
-from ..ops.gemv import MX_DECODE_MAX_ROWS, _mx_native_ok, mx_linear, mx_route, skinny_linear
+from ..ops.gemv import (MX_DECODE_MAX_ROWS, _FUSED_MX_ROWS_DEFAULT, _mx_native_ok, mx_decode_mfma_ok, mx_linear, mx_route,
+                        skinny_linear)
 from ..parallel_layers import parallel_state as ps
 from ..parallel_layers.parallel_state import get_tensor_model_parallel_size
 
@@ -62,7 +63,8 @@ _EMB_FUSED = os.environ.get("NXD_DECODE_EMB_FUSED", "1") == "1"
 # NXD_DECODE_FUSED_MX: a weight-quantized (MXFP4) Llama decodes at 1-3 rows on the fused launches of
 # csrc/decode_fused_mx.hip instead of the ten per-op launches per layer.  Read with NXD_DECODE_FUSED when
 # a model is first checked (_check_decode_fusable_mx).  The default is justified in the README
-# (Measured performance, fused MXFP4 decode).
+# (Measured performance, fused MXFP4 decode).  NXD_DECODE_FUSED_MX_ROWS (ops/gemv.py), read at the same
+# point, extends the route to 4-8 rows on csrc/decode_fused_mx_mfma.hip (_decode_fusable_mx_rows).
 _FUSED_MX_DEFAULT = "1"
 
 
@@ -166,7 +168,7 @@ class DecoderInferenceMixin:
         B, T = input_ids.shape
         if not prefill and self._decode_fusable(input_ids):
             return self._forward_decode_fused(input_ids, positions, seq_ids, cache_len, last_index, return_hidden)
-        if not prefill and self._decode_fusable_mx(input_ids):
+        if not prefill and (self._decode_fusable_mx(input_ids) or self._decode_fusable_mx_rows(input_ids)):
             return self._forward_decode_fused_mx(input_ids, positions, seq_ids, cache_len, last_index, return_hidden)
         nq, nkv, D = self.nq, self.nkv, self.head_dim
         W = (nq + 2 * nkv) * D
@@ -343,11 +345,24 @@ class DecoderInferenceMixin:
         return ok and input_ids.is_cuda and M <= MX_DECODE_MAX_ROWS and mx_route(M) == "gemv" and \
             M * self.config.hidden_size <= 32768
 
+    def _decode_fusable_mx_rows(self, input_ids: torch.Tensor) -> bool:
+        """The gate beside _decode_fusable_mx for 4-8 rows: the same launches with dgemv_mx on MFMA weight
+        tiles (csrc/decode_fused_mx_mfma.hip), when NXD_DECODE_FUSED_MX_ROWS admits the rows.  8 rows and
+        M * hidden <= 32768 are the limits of the bf16 QKV launch (its fused norm), as in the gates beside this one."""
+        ok = getattr(self, "_decode_fused_mx_ok", None)
+        if ok is None:
+            ok = self._check_decode_fusable_mx()
+            self._decode_fused_mx_ok = ok
+        M = input_ids.numel()
+        return ok and input_ids.is_cuda and M <= 8 and M * self.config.hidden_size <= 32768 and \
+            mx_decode_mfma_ok(M, getattr(self, "_decode_fused_mx_rows", 0))
+
     def _check_decode_fusable_mx(self) -> bool:
         """Whether a weight-quantized model decodes on the fused launches that read MXFP4
         (csrc/decode_fused_mx.hip): TP = 1, bf16 KV cache, bf16 bias-free QKV, every o_proj / gate_up /
         down and the lm_head bias-free MXFP4.  NXD_DECODE_FUSED_MX (default: _FUSED_MX_DEFAULT) and
-        NXD_DECODE_FUSED=0 switch it off."""
+        NXD_DECODE_FUSED=0 switch it off; NXD_DECODE_FUSED_MX_ROWS (ops/gemv.py) is read here as well."""
+        self._decode_fused_mx_rows = int(os.environ.get("NXD_DECODE_FUSED_MX_ROWS", str(_FUSED_MX_ROWS_DEFAULT)))
         if os.environ.get("NXD_DECODE_FUSED", "1") == "0" or \
                 os.environ.get("NXD_DECODE_FUSED_MX", _FUSED_MX_DEFAULT) == "0":
             return False

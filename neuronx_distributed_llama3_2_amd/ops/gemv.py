@@ -269,6 +269,22 @@ def mx_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, bias: 
 
 
 MX_DECODE_MAX_ROWS = 3
+# NXD_DECODE_FUSED_MX_ROWS: the largest row count that takes fused MXFP4 launches.  Rows 1..MX_DECODE_MAX_ROWS
+# are the VALU kernel (csrc/decode_fused_mx.hip) whatever it says; rows above, up to MX_DECODE_MFMA_MAX_ROWS, take
+# the kernel on MFMA weight tiles (csrc/decode_fused_mx_mfma.hip) when the knob admits them, so 3 is every route
+# before that kernel and values above 16 mean 16.  Read once per process here and when a model is first checked
+# (inference/model_base.py).  The default is justified in the README (Measured performance, fused MXFP4 decode
+# at 4-16 rows).
+MX_DECODE_MFMA_MAX_ROWS = 16
+_FUSED_MX_ROWS_DEFAULT = 16
+_FUSED_MX_ROWS = int(os.environ.get("NXD_DECODE_FUSED_MX_ROWS", str(_FUSED_MX_ROWS_DEFAULT)))
+
+
+def mx_decode_mfma_ok(M: int, knob: Optional[int] = None) -> bool:
+    """Whether M rows take the fused MXFP4 launch on MFMA weight tiles: above the VALU kernel's rows, admitted by
+    the knob (default: this module's NXD_DECODE_FUSED_MX_ROWS), and on rows mx_route gives the MFMA form."""
+    knob = _FUSED_MX_ROWS if knob is None else knob
+    return MX_DECODE_MAX_ROWS < M <= min(knob, MX_DECODE_MFMA_MAX_ROWS) and mx_route(M) == "gemm"
 
 
 def mx_decode_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, *,
@@ -283,7 +299,8 @@ def mx_decode_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor,
                               (o_proj, down)
 
     One launch each for at most MX_DECODE_MAX_ROWS bf16 rows on the GPU while mx_route keeps those rows
-    on the VALU kernel; every other case (and every other combination of the arguments) composes
+    on the VALU kernel, and for up to NXD_DECODE_FUSED_MX_ROWS (at most 16) rows on MFMA weight tiles
+    (mx_decode_mfma_ok); every other case (and every other combination of the arguments) composes
     ops.rms_norm, mx_linear and the add."""
     _check_mxfp4(packed, scale)
     K = x.shape[-1]
@@ -298,13 +315,15 @@ def mx_decode_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor,
     if residual is not None and (residual.shape[-1] != N or residual.numel() != M * N):
         raise ValueError(f"mx_decode_linear: residual {tuple(residual.shape)} against {M} rows of {N}")
     fused_form = (norm_weight is not None) != (residual is not None)   # a prologue or an epilogue, not both
-    if fused_form and use_native(x, packed, scale) and 1 <= M <= MX_DECODE_MAX_ROWS and mx_route(M) == "gemv" and \
+    mfma = mx_decode_mfma_ok(M)
+    if fused_form and use_native(x, packed, scale) and \
+            ((1 <= M <= MX_DECODE_MAX_ROWS and mx_route(M) == "gemv") or mfma) and \
             x.dtype == torch.bfloat16 and N >= 1 and _mx_native_ok(packed, scale) and \
             (Nw % 2 == 0 or not glu) and packed.stride(0) >= K // 2 and scale.stride(0) >= K // MX_BLOCK:
         y = None
         if residual is None:
             nw = norm_weight.contiguous()
-            if nw.dtype == torch.bfloat16 and nw.numel() == K and nw.data_ptr() % 16 == 0 and M * K <= 32768:
+            if nw.dtype == torch.bfloat16 and nw.numel() == K and nw.data_ptr() % 16 == 0 and (mfma or M * K <= 32768):
                 y = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
         elif residual.dtype == torch.bfloat16 and residual.device == x.device and residual.stride(-1) == 1 and \
                 (residual.is_contiguous() or (residual.dim() == 2 and residual.stride(0) >= N)):

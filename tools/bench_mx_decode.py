@@ -1,12 +1,14 @@
-"""Fused decode launches over MXFP4 weights (dgemv_mx, csrc/decode_fused_mx.hip) on one MI355X against what each
-replaces and against the bf16 fused launch of the same shape, on the Llama-3.2-1B / Llama-3-8B decode projections
-at 1-3 activation rows:
+"""Fused decode launches over MXFP4 weights (dgemv_mx: csrc/decode_fused_mx.hip at 1-3 rows, csrc/decode_fused_mx_mfma.hip
+at 4-16) on one MI355X against what each replaces and against the bf16 fused launch of the same shape, on the
+Llama-3.2-1B / Llama-3-8B decode projections at 1-16 activation rows (--rows, default 1,2,3):
 
   fused     one dgemv_mx launch: o_proj / down with the residual add, gate_up with RMSNorm + SwiGLU, norm + lm_head
-  unfused   the launches it replaces: rms_norm + mx_gemv (gate_up, lm_head), mx_gemv + add (o_proj, down)
-  bf16      dgemv (csrc/decode_fused.hip) with bf16 weights, same epilogue and prologue
+  unfused   the launches it replaces: rms_norm + mx_gemv (gate_up, lm_head), mx_gemv + add (o_proj, down); from 4 rows
+            mx_gemm (csrc/gemv_mx_mfma.hip) in place of mx_gemv, as ops.mx_linear routes them
+  bf16      dgemv (csrc/decode_fused.hip) with bf16 weights, same epilogue and prologue; it ends at 8 rows and at
+            M * K <= 32768 with a norm, beyond that the variant is left out
 
-The kernels are called directly, so the result does not depend on NXD_DECODE_FUSED_MX.  The variants alternate in
+The kernels are called directly, so the result does not depend on NXD_DECODE_FUSED_MX or NXD_DECODE_FUSED_MX_ROWS.  The variants alternate in
 one process; each is a captured hipGraph of calls that rotate over more than 512 MiB of weight copies (the Infinity
 Cache holds 256 MiB), so every call streams its weights from HBM.  One JSON line per (shape, rows, variant): median
 time per call over the rounds, its min / max (the run-to-run spread), the bytes the call must move (weights,
@@ -54,13 +56,20 @@ def call(kind, epi, x, nw, w, res):
         C.dgemv_mx(epi, x, norm, EPS, w[0], w[1], y, CFG)
     elif kind == "bf16":
         C.dgemv(epi, x, norm, EPS, w[0], y, 0, 0, 0, None, None, None, 1, None, None, None)
-    elif epi == RESID:
-        t = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-        C.mx_gemv(x, w[0], w[1], None, t, False)
-        res.add_(t)
     else:
-        C.mx_gemv(rms_norm(x, nw, EPS)[0], w[0], w[1], None, y, epi == GLU)
+        mx = C.mx_gemv if M <= 3 else C.mx_gemm
+        if epi == RESID:
+            t = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+            mx(x, w[0], w[1], None, t, False)
+            res.add_(t)
+        else:
+            mx(rms_norm(x, nw, EPS)[0], w[0], w[1], None, y, epi == GLU)
     return y
+
+
+def runs(kind, epi, M, K):
+    """Whether the variant exists at this shape (only the bf16 launch has limits inside 16 rows)."""
+    return kind != "bf16" or (M <= 8 and (epi == RESID or M * K <= 32768))
 
 
 def capture(kind, epi, x, nw, ws, res, inner):
@@ -101,9 +110,9 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_mx_decode needs a GPU")
     rows = [int(m) for m in a.rows.split(",")]
-    if any(not 1 <= m <= 3 for m in rows):
-        raise SystemExit("--rows: 1..3")
-    kinds = tuple(a.kinds.split(","))
+    if any(not 1 <= m <= 16 for m in rows):
+        raise SystemExit("--rows: 1..16")
+    all_kinds = tuple(a.kinds.split(","))
     sink = open(a.out, "a") if a.out else None
     for model in MODELS:
         if a.only and a.only != model:
@@ -112,9 +121,10 @@ def main():
             if a.ops and op not in a.ops.split(","):
                 continue
             N = Nw // 2 if epi == GLU else Nw
-            weights = {k: make_weights(k, Nw, K, max(2, -(-ROTATE_BYTES // weight_bytes(k, Nw, K)))) for k in kinds}
+            weights = {k: make_weights(k, Nw, K, max(2, -(-ROTATE_BYTES // weight_bytes(k, Nw, K)))) for k in all_kinds}
             nw = torch.ones(K, device="cuda", dtype=torch.bfloat16)
             for M in rows:
+                kinds = tuple(k for k in all_kinds if runs(k, epi, M, K))
                 x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
                 res = torch.zeros(M, N, device="cuda", dtype=torch.bfloat16)
                 inner = {k: 4 * len(weights[k]) for k in kinds}
