@@ -34,6 +34,7 @@ def main():
                          "all-reduces and vocabulary gather run on the one-shot peer kernels over IPC, so decode is "
                          "still captured in hipGraphs); prefill eager")
     ap.add_argument("--quantized", default=None, choices=[None, "per_tensor_symmetric", "per_channel_symmetric", "mxfp4"])
+    ap.add_argument("--quantize-qkv", action="store_true", help="with --quantized mxfp4: the fused QKV linear as MXFP4 too")
     ap.add_argument("--kv-cache-dtype", default=None, choices=[None, "bfloat16", "mxfp8"])
     ap.add_argument("--report", default="gpurun_out/benchmark_report.json")
     ap.add_argument("--weight-layout", action="store_true",
@@ -58,7 +59,7 @@ def main():
                            decode_graph_steps=args.graph_steps, use_hip_graphs=not args.no_graphs,
                            quantized=args.quantized is not None,
                            quantization_type=args.quantized or "per_tensor_symmetric",
-                           kv_cache_dtype=args.kv_cache_dtype)
+                           kv_cache_dtype=args.kv_cache_dtype, quantize_qkv=args.quantize_qkv)
     torch.manual_seed(0)
     model = LlamaForCausalLMInference(mcfg, icfg, dtype=torch.bfloat16)
     layouts = None
@@ -88,7 +89,7 @@ def main():
                                   "tokens_per_s_per_seq": 1000.0 * max(1, args.new - 1) / max(1e-6, e2e_ms - cte_ms)}
     report["config"] = {"model": args.model, "tp": world, "gloo_gpu_rehearsal": bool(args.gloo_gpu), "batch": args.batch, "prompt": args.prompt,
                         "new_tokens": args.new, "dtype": "bf16", "graph_steps": args.graph_steps,
-                        "hip_graphs": not args.no_graphs, "quantized": args.quantized, "kv_cache_dtype": args.kv_cache_dtype,
+                        "hip_graphs": not args.no_graphs, "quantized": args.quantized, "quantize_qkv": args.quantize_qkv, "kv_cache_dtype": args.kv_cache_dtype,
                         "weight_layouts": None if layouts is None else {v: sum(1 for x in layouts.values() if x == v)
                                                                         for v in set(layouts.values())},
                         "data": "synthetic prompt, random-init weights"}

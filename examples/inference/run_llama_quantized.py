@@ -29,12 +29,14 @@ def main(argv=None):
                    choices=["per_tensor_symmetric", "per_channel_symmetric", "mxfp4"])
     p.add_argument("--kv_cache_dtype", default=None, choices=["bfloat16", "mxfp8"],
                    help="mxfp8: E4M3 codes + E8M0 block scales in the KV cache (ops/decode.py), 33/64 of the bf16 bytes")
+    p.add_argument("--quantize-qkv", action="store_true",
+                   help="with --quantization_type mxfp4: store the fused QKV linear as MXFP4 too (default: activation dtype)")
     p.add_argument("--prompt_ids", action="append", default=None, help="comma-separated token ids")
     a = p.parse_args(argv)
     r = LlamaRunner(model_path=a.model_path, tokenizer_path=a.model_path)
     r.trace(a.traced_path, tp_degree=a.tp_degree, batch_size=1, max_prompt_length=a.max_prompt_length,
             sequence_length=a.sequence_length, quantized=True, quantization_type=a.quantization_type,
-            kv_cache_dtype=a.kv_cache_dtype)
+            kv_cache_dtype=a.kv_cache_dtype, quantize_qkv=a.quantize_qkv)
     model = r.load_neuron_model(a.traced_path)
     prompts = [[int(t) for t in s.split(",")] for s in (a.prompt_ids or ["1"])]
     out = r.generate_on_neuron(prompts, model)

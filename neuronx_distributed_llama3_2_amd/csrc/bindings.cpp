@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "decode_attn.h"
+#include "decode_fused_mx.h"
 
 #include <execinfo.h>
 #include <csignal>
@@ -77,10 +78,6 @@ void dgemv_set_knob(int, int);
 int dgemv_launch(int, const void*, int64_t, const void*, float, const void*, int64_t, void*, int64_t, int, int, int, int,
                  int, int, const float*, const float*, const int64_t*, int, void*, void*, int64_t, int64_t, int64_t,
                  const int*, int, int, const float*, float*, hipStream_t, const int64_t*, int64_t, void*, float*);
-int dgemv_mx_mfma_launch(int, const void*, int64_t, const void*, float, const void*, int64_t, const void*, int64_t, void*,
-                         int64_t, int, int, int, int, hipStream_t);
-int dgemv_mx_launch(int, const void*, int64_t, const void*, float, const void*, int64_t, const void*, int64_t, void*, int64_t,
-                    int, int, int, int, hipStream_t);
 int grouped_gemm_launch(int, const void*, const void*, void*, const int*, int, int, int, int, hipStream_t);
 int wgrad_gemm_launch(const void*, int64_t, const void*, int64_t, float*, int64_t, int, int, int, int, hipStream_t);
 int wgrad_gemm_choose_splits(int, int, int);
@@ -1357,13 +1354,37 @@ void dgemv(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, double e
 // launcher pick rows per wave R and k-slices KS; tests and the benchmark tool force them with cfg = 16 R + KS.
 // 4 <= M <= 16 is the kernel on MFMA weight tiles (csrc/decode_fused_mx_mfma.hip), where cfg = 16 T + KS forces the
 // tiles per wave T and the k-slices KS, and the fused norm has no M * K limit.
+// epi 3: the QKV projection with RoPE and the KV-cache write of dgemv's epi 3 (norm_w required; nq .. cache_idx as
+// there; T, R at most 2 in cfg); xidx: x is the embedding table and row m is x[xidx[m]], xcopy receives the rows.
 void dgemv_mx(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, double eps, at::Tensor w, at::Tensor scale,
-              at::Tensor y, int64_t cfg) {
+              at::Tensor y, int64_t cfg, int64_t nq, int64_t nkv, int64_t D, c10::optional<at::Tensor> cos_t,
+              c10::optional<at::Tensor> sin_t, c10::optional<at::Tensor> pos, int64_t T, c10::optional<at::Tensor> kc,
+              c10::optional<at::Tensor> vc, c10::optional<at::Tensor> cache_idx, c10::optional<at::Tensor> xidx,
+              c10::optional<at::Tensor> xcopy) {
   check_bf16(x, "x");
   check_bf16(y, "y");
-  TORCH_CHECK(epi >= 0 && epi <= 2, "dgemv_mx: epi must be 0..2");
+  TORCH_CHECK(epi >= 0 && epi <= 3, "dgemv_mx: epi must be 0..3");
   TORCH_CHECK(x.dim() == 2 && y.dim() == 2 && x.stride(1) == 1 && y.stride(1) == 1, "dgemv_mx: 2-D x / y, unit inner strides");
-  const int64_t M = x.size(0), K = x.size(1), N = y.size(1);
+  const int64_t M = xidx.has_value() ? xidx->numel() : x.size(0), K = x.size(1), N = y.size(1);
+  nxd::DgemvMxRope rope{};
+  if (xidx.has_value()) {
+    TORCH_CHECK(epi == 3, "dgemv_mx: xidx needs the QKV epilogue");
+    TORCH_CHECK(xidx->scalar_type() == at::kLong && xidx->is_contiguous() && xidx->is_cuda() && xidx->device() == x.device(),
+                "dgemv_mx: int64 xidx [M]");
+    TORCH_CHECK(x.size(0) >= 1, "dgemv_mx: empty embedding table");
+    rope.xidx = xidx->data_ptr<int64_t>();
+    rope.xrows = x.size(0);
+    if (xcopy.has_value()) {
+      check_bf16(*xcopy, "xcopy");
+      TORCH_CHECK(xcopy->is_contiguous() && xcopy->dim() == 2 && xcopy->size(0) == M && xcopy->size(1) == K &&
+                      xcopy->device() == x.device(),
+                  "dgemv_mx: xcopy bf16 contiguous [M, K]");
+      check_aligned16(*xcopy, "xcopy");
+      rope.xcopy = xcopy->data_ptr();
+    }
+  } else {
+    TORCH_CHECK(!xcopy.has_value(), "dgemv_mx: xcopy goes with xidx");
+  }
   check_mx(w, scale, K, "dgemv_mx");
   TORCH_CHECK(M >= 1 && M <= 16 && y.size(0) == M, "dgemv_mx: 1 <= M <= 16");
   TORCH_CHECK(N >= 1 && w.size(0) == (epi == 2 ? 2 * N : N), "dgemv_mx: weight shape mismatch");
@@ -1372,7 +1393,7 @@ void dgemv_mx(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, doubl
               "dgemv_mx: 16-byte aligned activation rows required");
   TORCH_CHECK(w.stride(0) >= K / 2 && scale.stride(0) >= K / 32, "dgemv_mx: weight / scale rows must not overlap");
   TORCH_CHECK(x.device() == w.device() && y.device() == w.device(), "dgemv_mx: operands on different devices");
-  TORCH_CHECK(norm_w.has_value() == (epi != 1), "dgemv_mx: epi 0 / 2 need the norm weight, epi 1 takes none");
+  TORCH_CHECK(norm_w.has_value() == (epi != 1), "dgemv_mx: epi 0 / 2 / 3 need the norm weight, epi 1 takes none");
   const void* nw = nullptr;
   if (norm_w.has_value()) {
     check_bf16(*norm_w, "norm_w");
@@ -1382,15 +1403,54 @@ void dgemv_mx(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, doubl
     nw = norm_w->data_ptr();
   }
   TORCH_CHECK(cfg == 0 || (cfg >= 17 && cfg <= 68), "dgemv_mx: cfg = 16 R + KS (4-16 rows: 16 T + KS)");
+  const nxd::DgemvMxRope* rp = nullptr;
+  if (epi == 3) {
+    TORCH_CHECK(cos_t.has_value() && sin_t.has_value() && pos.has_value() && kc.has_value() && vc.has_value(),
+                "dgemv_mx rope_kv: cos, sin, pos, k/v cache required");
+    TORCH_CHECK(D % 2 == 0 && D >= 2 && nq >= 1 && nkv >= 1 && N == (nq + 2 * nkv) * D, "dgemv_mx rope_kv: head layout");
+    TORCH_CHECK(cos_t->scalar_type() == at::kFloat && sin_t->scalar_type() == at::kFloat && cos_t->is_contiguous() &&
+                    sin_t->is_contiguous() && cos_t->dim() == 2 && cos_t->size(0) >= 1 && cos_t->size(1) == D / 2 &&
+                    sin_t->sizes() == cos_t->sizes(),
+                "dgemv_mx rope_kv: fp32 cos/sin tables [P, D/2]");
+    TORCH_CHECK(pos->scalar_type() == at::kLong && pos->is_contiguous() && pos->numel() == M, "dgemv_mx rope_kv: int64 pos [M]");
+    check_bf16(*kc, "k_cache");
+    check_bf16(*vc, "v_cache");
+    TORCH_CHECK(kc->dim() == 4 && kc->sizes() == vc->sizes() && kc->strides() == vc->strides() && kc->stride(3) == 1 &&
+                    kc->size(1) == nkv && kc->size(3) == D,
+                "dgemv_mx rope_kv: caches [B, Hkv, Lmax, D]");
+    TORCH_CHECK(T >= 1 && M % T == 0, "dgemv_mx rope_kv: rows must be whole sequences of T tokens");
+    if (cache_idx.has_value()) {
+      TORCH_CHECK(cache_idx->scalar_type() == at::kInt && cache_idx->is_contiguous() && cache_idx->numel() == M / T,
+                  "dgemv_mx rope_kv: int32 cache_idx [B]");
+      rope.cache_idx = cache_idx->data_ptr<int>();
+    } else {
+      TORCH_CHECK(kc->size(0) >= M / T, "dgemv_mx rope_kv: cache batch");
+    }
+    TORCH_CHECK(cos_t->device() == w.device() && sin_t->device() == w.device() && pos->device() == w.device() &&
+                    kc->device() == w.device() && vc->device() == w.device() &&
+                    (!cache_idx.has_value() || cache_idx->device() == w.device()),
+                "dgemv_mx rope_kv: operands on different devices");
+    rope.nq = (int)nq, rope.nkv = (int)nkv, rope.D = (int)D;
+    rope.cos_t = cos_t->data_ptr<float>();
+    rope.sin_t = sin_t->data_ptr<float>();
+    rope.pos = pos->data_ptr<int64_t>();
+    rope.T = (int)T;
+    rope.kc = kc->data_ptr();
+    rope.vc = vc->data_ptr();
+    rope.c_sb = kc->stride(0), rope.c_sh = kc->stride(1), rope.c_sl = kc->stride(2);
+    rope.Lmax = (int)kc->size(2);
+    rope.max_pos = (int)cos_t->size(0);
+    rp = &rope;
+  }
   int rc;
   if (M > 3) {   // MFMA weight tiles (csrc/decode_fused_mx_mfma.hip)
     rc = nxd::dgemv_mx_mfma_launch((int)epi, x.data_ptr(), x.stride(0), nw, (float)eps, w.data_ptr(), w.stride(0),
                                    scale.data_ptr(), scale.stride(0), y.data_ptr(), y.stride(0), (int)M, (int)N, (int)K,
-                                   (int)cfg, cur_stream());
+                                   (int)cfg, cur_stream(), rp);
   } else {
     rc = nxd::dgemv_mx_launch((int)epi, x.data_ptr(), x.stride(0), nw, (float)eps, w.data_ptr(), w.stride(0),
                               scale.data_ptr(), scale.stride(0), y.data_ptr(), y.stride(0), (int)M, (int)N, (int)K, (int)cfg,
-                              cur_stream());
+                              cur_stream(), rp);
   }
   check_rc(rc, "dgemv_mx");
 }
@@ -1499,7 +1559,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("kc"), py::arg("vc"), py::arg("cache_idx"), py::arg("xadd") = py::none(), py::arg("yadd") = py::none(),
         py::arg("xidx") = py::none(), py::arg("xcopy") = py::none());
   m.def("dgemv_mx", &dgemv_mx, py::arg("epi"), py::arg("x"), py::arg("norm_w"), py::arg("eps"), py::arg("w"), py::arg("scale"),
-        py::arg("y"), py::arg("cfg") = 0);
+        py::arg("y"), py::arg("cfg") = 0, py::kw_only(), py::arg("nq") = 0, py::arg("nkv") = 0, py::arg("D") = 0,
+        py::arg("cos_t") = py::none(), py::arg("sin_t") = py::none(), py::arg("pos") = py::none(), py::arg("T") = 1,
+        py::arg("kc") = py::none(), py::arg("vc") = py::none(), py::arg("cache_idx") = py::none(),
+        py::arg("xidx") = py::none(), py::arg("xcopy") = py::none());
   // decode A/B knobs: 0 = GLU row pairs per wave, 1 = GEMV k-slices (0 auto), 2 = MFMA decode attention on/off,
   // 3 = GEMV early epilogue / prologue reads on/off, 5 = bs = 1 GEMV forced occupancy (0 natural | 7 | 8 waves / SIMD)
   m.def("decode_set_knob", [](int which, int value) {

@@ -49,6 +49,11 @@ class InferenceConfig:
         self.quantized_checkpoints_path = kwargs.pop("quantized_checkpoints_path", None)
         # "per_tensor_symmetric" / "per_channel_symmetric" (int8) or "mxfp4" (block-scaled 4-bit)
         self.quantization_type = kwargs.pop("quantization_type", "per_tensor_symmetric")
+        # with quantization_type="mxfp4": also store the fused GQA QKV linear as MXFP4 (default: it stays
+        # in the activation dtype)
+        self.quantize_qkv = bool(kwargs.pop("quantize_qkv", False))
+        if self.quantize_qkv and self.quantized and str(self.quantization_type) != "mxfp4":
+            raise ValueError(f"quantize_qkv needs quantization_type='mxfp4', got {self.quantization_type!r}")
         # KV-cache storage: None / "bfloat16" (the activation dtype) or "mxfp8" (E4M3 codes + E8M0 block
         # scales, 33/64 of the bytes; format in ops/decode.py)
         self.kv_cache_dtype = kwargs.pop("kv_cache_dtype", None)

@@ -207,11 +207,18 @@ class LlamaForCausalLMInference:
                                     get_default_per_channel_custom_qconfig_dict)
 
         qt = str(self.config.quantization_type)
+        mapping = None
+        if getattr(self.config, "quantize_qkv", False) and qt != "mxfp4":
+            raise ValueError(f"quantize_qkv needs quantization_type='mxfp4', got {qt!r}")
         if qt == "mxfp4":   # MXFP4 weight-only layers (quantization_layers.MXFP4*Parallel)
             q = get_default_mxfp4_qconfig_dict()
+            if getattr(self.config, "quantize_qkv", False):   # + the fused QKV linear
+                from ..quantization import get_mxfp4_quant_module_mappings, with_mxfp4_qkv
+
+                mapping = with_mxfp4_qkv(get_mxfp4_quant_module_mappings())
         else:
             q = get_default_per_channel_custom_qconfig_dict() if "channel" in qt else get_default_custom_qconfig_dict()
-        convert(self.model, q, inplace=True)
+        convert(self.model, q, inplace=True, mapping=mapping)
 
     # ------------------------------------------------------------------ construction
     @classmethod

@@ -354,13 +354,19 @@ class DecoderInferenceMixin:
             ok = self._check_decode_fusable_mx()
             self._decode_fused_mx_ok = ok
         M = input_ids.numel()
+        rows = getattr(self, "_decode_fused_mx_rows", 0)
+        if ok and getattr(self, "_decode_fused_mx_qkv", False):
+            # packed QKV (dgemv_mx's QKV form on MFMA weight tiles): up to 16 rows, no M * hidden limit
+            return input_ids.is_cuda and (self.head_dim // 2) % 16 == 0 and mx_decode_mfma_ok(M, min(rows, 16))
         return ok and input_ids.is_cuda and M <= 8 and M * self.config.hidden_size <= 32768 and \
-            mx_decode_mfma_ok(M, getattr(self, "_decode_fused_mx_rows", 0))
+            mx_decode_mfma_ok(M, rows)
 
     def _check_decode_fusable_mx(self) -> bool:
         """Whether a weight-quantized model decodes on the fused launches that read MXFP4
-        (csrc/decode_fused_mx.hip): TP = 1, bf16 KV cache, bf16 bias-free QKV, every o_proj / gate_up /
-        down and the lm_head bias-free MXFP4.  NXD_DECODE_FUSED_MX (default: _FUSED_MX_DEFAULT) and
+        (csrc/decode_fused_mx.hip): TP = 1, bf16 KV cache, bias-free QKV that is bf16 in every layer or packed
+        MXFP4 in every layer (remembered in _decode_fused_mx_qkv; from 4 rows the packed form needs
+        (head_dim / 2) % 16 == 0, else those rows stay unfused), every o_proj / gate_up / down and the lm_head
+        bias-free MXFP4.  NXD_DECODE_FUSED_MX (default: _FUSED_MX_DEFAULT) and
         NXD_DECODE_FUSED=0 switch it off; NXD_DECODE_FUSED_MX_ROWS (ops/gemv.py) is read here as well."""
         self._decode_fused_mx_rows = int(os.environ.get("NXD_DECODE_FUSED_MX_ROWS", str(_FUSED_MX_ROWS_DEFAULT)))
         if os.environ.get("NXD_DECODE_FUSED", "1") == "0" or \
@@ -372,19 +378,30 @@ class DecoderInferenceMixin:
             return False
         if self.head_dim % 2 or self.head_dim > 256:
             return False
+        packed_qkv = set()
         for layer in self.model.layers:
             attn = layer.self_attn
             w, b = attn.qkv_proj._fused_weight_bias() if hasattr(attn.qkv_proj, "_fused_weight_bias") \
                 else (attn.qkv_proj.weight, getattr(attn.qkv_proj, "bias", None))
-            if b is not None or w.dtype != torch.bfloat16:
+            if b is not None:
                 return False
+            if w.dtype == torch.uint8:
+                s = getattr(attn.qkv_proj, "scale", None)
+                if s is None or s.dtype != torch.uint8 or not _mx_native_ok(w, s):
+                    return False
+            elif w.dtype != torch.bfloat16:
+                return False
+            packed_qkv.add(w.dtype == torch.uint8)
             if not self._mx_packed(attn.o_proj) or self._fused_mx_ffn_weights(layer) is None:
                 return False
+        if len(packed_qkv) != 1:
+            return False
+        self._decode_fused_mx_qkv = packed_qkv.pop()
         return self._mx_packed(self.lm_head)
 
     def _forward_decode_fused_mx(self, input_ids, positions, seq_ids, cache_len, last_index, return_hidden):
-        """_forward_decode_fused for MXFP4 projections: per layer dgemv(QKV + RoPE + cache write, bf16),
-        decode attention, dgemv_mx(o_proj + residual), dgemv_mx(norm + gate_up + SwiGLU),
+        """_forward_decode_fused for MXFP4 projections: per layer dgemv(QKV + RoPE + cache write, bf16; with a
+        packed QKV the same launch on the 4-bit weight, dgemv_mx(3)), decode attention, dgemv_mx(o_proj + residual), dgemv_mx(norm + gate_up + SwiGLU),
         dgemv_mx(down + residual); then dgemv_mx(final norm + lm_head).  Static shapes, no host sync."""
         C = ops.ext()
         B, T = input_ids.shape
@@ -410,7 +427,12 @@ class DecoderInferenceMixin:
             w_qkv = attn.qkv_proj._fused_weight_bias()[0] if hasattr(attn.qkv_proj, "_fused_weight_bias") \
                 else attn.qkv_proj.weight
             kc, vc = self.kv_cache[i, 0], self.kv_cache[i, 1]
-            if i == 0 and emb_fused:
+            if w_qkv.dtype == torch.uint8:   # packed QKV
+                gather = dict(xidx=ids, xcopy=res) if i == 0 and emb_fused else {}
+                C.dgemv_mx(3, ew if gather else res, layer.input_layernorm.weight, self.eps, w_qkv, attn.qkv_proj.scale, qkv,
+                           nq=nq, nkv=nkv, D=D, cos_t=cos_t, sin_t=sin_t, pos=pos, T=T, kc=kc, vc=vc, cache_idx=sid32,
+                           **gather)
+            elif i == 0 and emb_fused:
                 C.dgemv(3, ew, layer.input_layernorm.weight, self.eps, w_qkv, qkv, nq, nkv, D, cos_t, sin_t, pos, T,
                         kc, vc, sid32, xidx=ids, xcopy=res)
             else:

@@ -47,14 +47,19 @@ class _MoEInferenceBase(LlamaForCausalLMInference):
 
     def _quantize(self) -> None:
         """quantization_type="mxfp4": o_proj, the lm_head and the expert linears become MXFP4 weight-only
-        layers (quantization_layers.MXFP4*); the router and the fused QKV stay in the activation dtype."""
-        from ..quantization import convert, get_default_mxfp4_qconfig_dict, get_mxfp4_moe_quant_module_mappings
+        layers (quantization_layers.MXFP4*); the router stays in the activation dtype, and so does the fused
+        QKV unless InferenceConfig(quantize_qkv=True)."""
+        from ..quantization import (convert, get_default_mxfp4_qconfig_dict, get_mxfp4_moe_quant_module_mappings,
+                                    with_mxfp4_qkv)
 
         qt = str(self.config.quantization_type)
         if qt != "mxfp4":
             raise NotImplementedError(f"quantization_type={qt!r}: the MoE applications implement MXFP4 weight-only "
                                       "quantization only; int8 MoE experts are not implemented for inference")
-        convert(self.model, get_default_mxfp4_qconfig_dict(), inplace=True, mapping=get_mxfp4_moe_quant_module_mappings())
+        mapping = get_mxfp4_moe_quant_module_mappings()
+        if getattr(self.config, "quantize_qkv", False):
+            mapping = with_mxfp4_qkv(mapping)
+        convert(self.model, get_default_mxfp4_qconfig_dict(), inplace=True, mapping=mapping)
 
     def _load_full(self, full_sd) -> None:
         """The packed expert parameters are output-major ([E, out, in/2]) while a full float expert

@@ -347,6 +347,70 @@ def mx_decode_linear(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor,
     return residual
 
 
+def mx_decode_qkv(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, norm_weight: torch.Tensor, eps: float,
+                  nq: int, nkv: int, D: int, cos_t: torch.Tensor, sin_t: torch.Tensor, pos: torch.Tensor, T: int,
+                  kc: torch.Tensor, vc: torch.Tensor, cache_idx: Optional[torch.Tensor] = None,
+                  xidx: Optional[torch.Tensor] = None, xcopy: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The decode QKV projection over an MXFP4 fused weight W [(nq + 2 nkv) D, K]: RMSNorm(x) @ deq(W)^T, the
+    q and k heads rotated (rotate-half pairs, fp32 cos / sin tables [max_pos, D/2] at pos [M]), q | k | v returned
+    as [M, (nq + 2 nkv) D], and k, v written into the bf16 caches [B, nkv, Lmax, D] at (cache_idx[m // T] or
+    m // T, head, pos[m]) for positions inside the cache.  With xidx [M], x is the embedding table and row m is
+    x[xidx[m]] (a zero row for an id outside it); xcopy [M, K], if given, receives the rows.
+
+    One launch (csrc/decode_fused_mx.hip at 1-3 rows with M * K <= 32768, csrc/decode_fused_mx_mfma.hip up to
+    NXD_DECODE_FUSED_MX_ROWS rows when (D / 2) % 16 == 0) for bf16 operands on the GPU; everything else composes
+    ops.rms_norm, mx_linear, the rotation and ops.kv_cache_write, which takes the T positions of a sequence
+    as consecutive."""
+    _check_mxfp4(packed, scale)
+    K = x.shape[-1]
+    W = (nq + 2 * nkv) * D
+    if packed.dim() != 2 or packed.shape[1] * 2 != K or packed.shape[0] != W:
+        raise ValueError(f"mx_decode_qkv: x [..., {K}] and {nq} + 2 * {nkv} heads of {D} against packed weight "
+                         f"{tuple(packed.shape)}")
+    M = xidx.numel() if xidx is not None else x.numel() // K
+    if pos.numel() != M or T < 1 or M % T:
+        raise ValueError(f"mx_decode_qkv: {M} rows, pos {tuple(pos.shape)}, T {T}")
+    mfma = mx_decode_mfma_ok(M) and (D // 2) % 16 == 0 and D % 2 == 0
+    valu = 1 <= M <= MX_DECODE_MAX_ROWS and mx_route(M) == "gemv" and M * K <= 32768 and D % 2 == 0
+    nw = norm_weight.contiguous()
+    if use_native(x, packed, scale, kc, vc) and (valu or mfma) and x.dtype == torch.bfloat16 and \
+            _mx_native_ok(packed, scale) and packed.stride(0) >= K // 2 and scale.stride(0) >= K // MX_BLOCK and \
+            nw.dtype == torch.bfloat16 and nw.numel() == K and nw.data_ptr() % 16 == 0 and \
+            kc.dtype == torch.bfloat16 and vc.dtype == torch.bfloat16 and kc.stride() == vc.stride() and kc.stride(3) == 1 and \
+            cos_t.dtype == torch.float32 and sin_t.dtype == torch.float32 and \
+            (xidx is None or (x.dim() == 2 and xidx.dtype == torch.int64)):
+        x2 = x if xidx is not None else x.reshape(M, K)
+        if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.stride(0) < K or x2.data_ptr() % 16:
+            x2 = x2.contiguous()
+        y = torch.empty((M, W), dtype=torch.bfloat16, device=x.device)
+        ext().dgemv_mx(3, x2, nw, float(eps), packed, scale, y, nq=nq, nkv=nkv, D=D, cos_t=cos_t.contiguous(),
+                       sin_t=sin_t.contiguous(), pos=pos.reshape(-1).to(torch.int64).contiguous(), T=T, kc=kc, vc=vc,
+                       cache_idx=cache_idx.to(torch.int32).contiguous() if cache_idx is not None else None,
+                       xidx=xidx.reshape(-1).contiguous() if xidx is not None else None, xcopy=xcopy)
+        return y
+    from .decode import kv_cache_write
+    from .norm import rms_norm
+    from .rope import _rope_ref_, rope_inplace_
+
+    if xidx is not None:
+        from .embedding import vocab_parallel_embedding
+
+        x = vocab_parallel_embedding(xidx.reshape(-1), x, 0)
+        if xcopy is not None:
+            xcopy.copy_(x)
+    h = rms_norm(x.reshape(M, K), nw, eps)[0]
+    y = mx_linear(h, packed, scale, None).contiguous()
+    p = pos.reshape(-1).to(torch.int64)
+    pt = p.clamp(0, cos_t.shape[0] - 1)
+    if D in (64, 128, 256):
+        rope_inplace_(y, 0, nq + nkv, D, cos_t, sin_t, pt)
+    else:   # a head dim the rotation kernel does not take: the same fp32 rotation in torch
+        _rope_ref_(y, 0, nq + nkv, D, cos_t.to(y.device), sin_t.to(y.device), pt, 1.0)
+    heads = y.view(M // T, T, nq + 2 * nkv, D)
+    kv_cache_write(heads[:, :, nq:nq + nkv], heads[:, :, nq + nkv:], kc, vc, p.view(M // T, T)[:, 0].to(torch.int32), cache_idx)
+    return y
+
+
 def _check_mx_stack(x: torch.Tensor, packed: torch.Tensor, scale: torch.Tensor, glu: bool, op: str) -> None:
     _check_mxfp4(packed, scale)
     if packed.dim() != 3 or packed.shape[2] * 2 != x.shape[-1]:

@@ -15,6 +15,7 @@ from .quantization_layers import (  # noqa: F401
     MXFP4ColumnParallel,
     MXFP4ExpertFusedColumnParallel,
     MXFP4ExpertFusedRowParallel,
+    MXFP4GQAQKVColumnParallel,
     MXFP4RowParallel,
     QuantizedColumnParallel,
     QuantizedExpertFusedColumnParallel,
@@ -28,5 +29,5 @@ from .quantization_utils import (  # noqa: F401
     quantize_pytorch_model_per_channel_symmetric,
     quantize_pytorch_model_per_tensor_symmetric,
 )
-from .quantization_mappings import get_mxfp4_moe_quant_module_mappings  # noqa: F401
+from .quantization_mappings import get_mxfp4_moe_quant_module_mappings, get_mxfp4_quant_module_mappings, with_mxfp4_qkv  # noqa: F401
 from .quantize import convert  # noqa: F401

@@ -372,6 +372,105 @@ class MXFP4RowParallel(_MXFP4ParallelLinear):
         return new
 
 
+class MXFP4GQAQKVColumnParallel(nn.Module):
+    """MXFP4 storage of the fused GQA QKV linear (modules/qkv_linear.py, fuse_qkv=True): `weight_qkv` is the
+    packed uint8 [q_local + 2 kv_local, in/2] parameter, `scale_qkv` the E8M0 uint8 [.., in/32] one.  Blocks
+    run along the in-features, so a TP row shard of either tensor is the row shard of the float weight's
+    quantization: both carry the float layer's sharding attributes (fused_qkv, qkv_split).  The bias, if
+    any, stays in the activation dtype.  `_fused_weight_bias()` / `.scale` are what the inference forward
+    reads (DecoderInferenceMixin._proj -> mx_linear; the fused decode launch: ops.gemv.mx_decode_qkv)."""
+
+    def __init__(self, input_size: int, output_sizes, bias: bool = True, gather_output: bool = True,
+                 dtype: torch.dtype = torch.bfloat16, device: Optional[torch.device] = None,
+                 sequence_parallel_enabled: bool = False, kv_size_multiplier: int = 1, fuse_qkv: bool = True,
+                 q_config: Optional[dict] = None, **kw):
+        super().__init__()
+        if not fuse_qkv:
+            raise NotImplementedError("MXFP4GQAQKVColumnParallel holds the fused QKV weight only (fuse_qkv=True)")
+        if input_size % MX_BLOCK != 0:
+            raise ValueError(f"MXFP4 needs the in-features ({input_size}) to be a multiple of {MX_BLOCK}")
+        tp = ps.get_tensor_model_parallel_size()
+        self.input_size, self.output_sizes = input_size, list(output_sizes)
+        self.gather_output, self.dtype, self.fuse_qkv, self.use_bias = gather_output, dtype, True, bias
+        self.kv_size_multiplier = kv_size_multiplier
+        self.sequence_parallel_enabled = sequence_parallel_enabled and tp > 1
+        self.q_output_size_per_partition = divide(self.output_sizes[0], tp)
+        self.kv_output_size_per_partition = divide(self.output_sizes[1] * kv_size_multiplier, tp)
+        self.quantization_type = QuantizationType.MX_BLOCK
+        self.quantized_dtype = QuantizedDtype.MXFP4.value
+        rows = self.q_output_size_per_partition + 2 * self.kv_output_size_per_partition
+        self.weight_qkv = Parameter(torch.zeros((rows, input_size // 2), dtype=torch.uint8, device=device),
+                                    requires_grad=False)
+        # e = 127 (scale 1) with zero codes: an unloaded layer dequantises to zeros
+        self.scale_qkv = Parameter(torch.full((rows, input_size // MX_BLOCK), 127, dtype=torch.uint8, device=device),
+                                   requires_grad=False)
+        split = (self.output_sizes[0], self.output_sizes[1], kv_size_multiplier)
+        tensors = [self.weight_qkv, self.scale_qkv]
+        if bias:
+            self.bias_qkv = Parameter(torch.zeros(rows, dtype=dtype, device=device), requires_grad=False)
+            tensors.append(self.bias_qkv)
+        else:
+            self.bias_qkv = None
+        for t in tensors:
+            set_tensor_model_parallel_attributes(t, True, 0, 1)
+            setattr(t, "qkv_split", split)
+        for t in tensors[:2]:
+            setattr(t, "fused_qkv", True)
+            setattr(t, "num_partitions", tp)
+
+    @property
+    def scale(self) -> torch.Tensor:
+        return self.scale_qkv
+
+    def _fused_weight_bias(self):
+        return self.weight_qkv, self.bias_qkv
+
+    def quantize_from(self, w_float: torch.Tensor) -> None:
+        """Quantise a float fused weight of this layer's (local) [q + 2 kv, in] shape."""
+        q, s = quantize_mxfp4(w_float)
+        with torch.no_grad():
+            self.weight_qkv.copy_(q.to(self.weight_qkv.device))
+            self.scale_qkv.copy_(s.to(self.scale_qkv.device))
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                              error_msgs):
+        wk = prefix + "weight_qkv"
+        if wk in state_dict and state_dict[wk].is_floating_point():
+            state_dict[wk], state_dict[prefix + "scale_qkv"] = quantize_mxfp4(state_dict[wk])
+        super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
+                                      error_msgs)
+
+    def forward_fused(self, x: torch.Tensor) -> torch.Tensor:
+        """[.., H] -> [.., q_local + 2 * kv_local]."""
+        if self.sequence_parallel_enabled:
+            x = sp.sp_gather(x)
+        return mx_linear(x, self.weight_qkv, self.scale_qkv, self.bias_qkv)
+
+    def forward(self, x: torch.Tensor):
+        out = self.forward_fused(x)
+        q_l, kv_l = self.q_output_size_per_partition, self.kv_output_size_per_partition
+        q, k, v = out[..., :q_l], out[..., q_l:q_l + kv_l], out[..., q_l + kv_l:]
+        if self.gather_output:
+            q, k, v = (mappings.gather_from_tensor_model_parallel_region(t) for t in (q, k, v))
+        return q, k, v
+
+    @classmethod
+    def from_float(cls, mod, q_config: BASE_QCONFIG_DICT_TYPE = None):
+        if not mod.fuse_qkv:
+            raise NotImplementedError("MXFP4 QKV needs the fused QKV weight (fuse_qkv=True)")
+        w = mod.weight_qkv
+        new = cls(mod.input_size, mod.output_sizes, bias=mod.use_bias, gather_output=mod.gather_output,
+                  dtype=w.dtype if w.is_floating_point() else torch.bfloat16, device=w.device,
+                  sequence_parallel_enabled=mod.sequence_parallel_enabled, kv_size_multiplier=mod.kv_size_multiplier,
+                  q_config=q_config)
+        if w.device.type != "meta":
+            new.quantize_from(w)
+            if mod.bias_qkv is not None:
+                with torch.no_grad():
+                    new.bias_qkv.copy_(mod.bias_qkv)
+        return new
+
+
 class _MXFP4ExpertFused(nn.Module):
     """MXFP4 storage of an expert-fused linear (logical weight [E, in, out]): `weight` is the packed
     uint8 [E, out_local, in_local/2] parameter, `scale` the E8M0 uint8 [E, out_local, in_local/32] one

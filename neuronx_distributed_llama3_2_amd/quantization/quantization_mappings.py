@@ -32,6 +32,14 @@ MXFP4_MOE_QUANT_MODULE_MAPPINGS: Dict[Callable, Any] = {
 }
 
 
+def with_mxfp4_qkv(mapping: Dict[Callable, Any]) -> Dict[Callable, Any]:
+    """`mapping` plus the fused GQA QKV linear (InferenceConfig(quantize_qkv=True)): the default MXFP4
+    mappings leave it in the activation dtype."""
+    from ..modules.qkv_linear import GQAQKVColumnParallelLinear
+
+    return {**mapping, GQAQKVColumnParallelLinear: q_layers.MXFP4GQAQKVColumnParallel}
+
+
 def get_mxfp4_moe_quant_module_mappings() -> Dict[Callable, Any]:
     return MXFP4_MOE_QUANT_MODULE_MAPPINGS
 

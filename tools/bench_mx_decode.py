@@ -2,9 +2,11 @@
 at 4-16) on one MI355X against what each replaces and against the bf16 fused launch of the same shape, on the
 Llama-3.2-1B / Llama-3-8B decode projections at 1-16 activation rows (--rows, default 1,2,3):
 
-  fused     one dgemv_mx launch: o_proj / down with the residual add, gate_up with RMSNorm + SwiGLU, norm + lm_head
+  fused     one dgemv_mx launch: o_proj / down with the residual add, gate_up with RMSNorm + SwiGLU, norm + lm_head,
+            qkv with RMSNorm, RoPE and the KV-cache write
   unfused   the launches it replaces: rms_norm + mx_gemv (gate_up, lm_head), mx_gemv + add (o_proj, down); from 4 rows
-            mx_gemm (csrc/gemv_mx_mfma.hip) in place of mx_gemv, as ops.mx_linear routes them
+            mx_gemm (csrc/gemv_mx_mfma.hip) in place of mx_gemv, as ops.mx_linear routes them; qkv: rms_norm + mx_gemv /
+            mx_gemm + rope_inplace_ + kv_cache_write
   bf16      dgemv (csrc/decode_fused.hip) with bf16 weights, same epilogue and prologue; it ends at 8 rows and at
             M * K <= 32768 with a norm, beyond that the variant is left out
 
@@ -21,10 +23,13 @@ import sys
 import torch
 
 sys.path.insert(0, ".")
-from neuronx_distributed_llama3_2_amd.ops import ext, rms_norm  # noqa: E402
+from neuronx_distributed_llama3_2_amd.ops import ext, kv_cache_write, rms_norm, rope_inplace_  # noqa: E402
 
-PLAIN, RESID, GLU = 0, 1, 2
+PLAIN, RESID, GLU, QKV = 0, 1, 2, 3
 MODELS = {"llama3.2-1b": (2048, 8192, 128256), "llama3-8b": (4096, 14336, 128256)}   # hidden, intermediate, vocabulary
+HEADS = {2048: (32, 8, 64), 4096: (32, 8, 128)}   # by hidden size: q heads, kv heads, head dim
+LMAX = 64   # positions of the qkv shape's KV caches; every row writes position 7 of its own sequence
+_ROPE = {}
 ROTATE_BYTES = 512 << 20
 EPS = 1e-5
 CFG = 0   # --cfg: force dgemv_mx's rows per wave R and k-slices KS (16 R + KS); 0 = the launcher's choice
@@ -32,7 +37,21 @@ CFG = 0   # --cfg: force dgemv_mx's rows per wave R and k-slices KS (16 R + KS);
 
 def shapes(model):
     H, I, V = MODELS[model]   # op, epilogue, K, weight rows
-    return [("o_proj", RESID, H, H), ("gate_up", GLU, H, 2 * I), ("down", RESID, I, H), ("lm_head", PLAIN, H, V)]
+    nq, nkv, D = HEADS[H]
+    return [("o_proj", RESID, H, H), ("gate_up", GLU, H, 2 * I), ("down", RESID, I, H), ("lm_head", PLAIN, H, V),
+            ("qkv", QKV, H, (nq + 2 * nkv) * D)]
+
+
+def rope_operands(M, K):
+    """cos / sin tables, positions and the bf16 KV caches of the qkv shape at M rows (one token per sequence)."""
+    if (M, K) not in _ROPE:
+        nq, nkv, D = HEADS[K]
+        ang = torch.rand(LMAX, D // 2, device="cuda") * 6.28
+        _ROPE[(M, K)] = dict(nq=nq, nkv=nkv, D=D, cos_t=ang.cos(), sin_t=ang.sin(), T=1,
+                             pos=torch.full((M,), 7, dtype=torch.int64, device="cuda"),
+                             kc=torch.zeros(M, nkv, LMAX, D, device="cuda", dtype=torch.bfloat16),
+                             vc=torch.zeros(M, nkv, LMAX, D, device="cuda", dtype=torch.bfloat16))
+    return _ROPE[(M, K)]
 
 
 def weight_bytes(kind, Nw, K):
@@ -52,7 +71,18 @@ def call(kind, epi, x, nw, w, res):
     M, N = x.shape[0], w[0].shape[0] // (2 if epi == GLU else 1)
     y = res if epi == RESID else torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
     norm = None if epi == RESID else nw
-    if kind == "fused":
+    if epi == QKV:
+        r = rope_operands(M, x.shape[1])
+        if kind == "fused":
+            C.dgemv_mx(epi, x, nw, EPS, w[0], w[1], y, CFG, **r)
+        elif kind == "bf16":
+            C.dgemv(epi, x, nw, EPS, w[0], y, r["nq"], r["nkv"], r["D"], r["cos_t"], r["sin_t"], r["pos"], 1, r["kc"], r["vc"], None)
+        else:
+            (C.mx_gemv if M <= 3 else C.mx_gemm)(rms_norm(x, nw, EPS)[0], w[0], w[1], None, y, False)
+            rope_inplace_(y, 0, r["nq"] + r["nkv"], r["D"], r["cos_t"], r["sin_t"], r["pos"])
+            h = y.view(M, 1, r["nq"] + 2 * r["nkv"], r["D"])
+            kv_cache_write(h[:, :, r["nq"]:r["nq"] + r["nkv"]], h[:, :, r["nq"] + r["nkv"]:], r["kc"], r["vc"], r["pos"].to(torch.int32))
+    elif kind == "fused":
         C.dgemv_mx(epi, x, norm, EPS, w[0], w[1], y, CFG)
     elif kind == "bf16":
         C.dgemv(epi, x, norm, EPS, w[0], y, 0, 0, 0, None, None, None, 1, None, None, None)
@@ -101,7 +131,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--rows", default="1,2,3")
     ap.add_argument("--only", default=None, help="model name filter")
-    ap.add_argument("--ops", default=None, help="comma-separated projection filter (o_proj,gate_up,down,lm_head)")
+    ap.add_argument("--ops", default=None, help="comma-separated projection filter (o_proj,gate_up,down,lm_head,qkv)")
     ap.add_argument("--kinds", default="fused,unfused,bf16")
     ap.add_argument("--cfg", type=int, default=0, help="force dgemv_mx's rows per wave R and k-slices KS: 16 R + KS")
     a = ap.parse_args()
