@@ -611,12 +611,35 @@ at::Tensor mx8_dequant(at::Tensor codes, at::Tensor scale) {
   return out;
 }
 
+void kv_cache_write(at::Tensor k, at::Tensor v, at::Tensor kc, at::Tensor vc, c10::optional<at::Tensor> cache_idx,
+                    at::Tensor pos, c10::optional<at::Tensor> k_scale, c10::optional<at::Tensor> v_scale);
+
 void decode_attn(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional<at::Tensor> cache_idx, at::Tensor seq_len,
                  at::Tensor out, double scale, int64_t nsplit, int64_t window, c10::optional<at::Tensor> k_scale,
-                 c10::optional<at::Tensor> v_scale) {
+                 c10::optional<at::Tensor> v_scale, c10::optional<at::Tensor> k_new, c10::optional<at::Tensor> v_new,
+                 c10::optional<at::Tensor> pos) {
   int64_t qs[3], os[3];
   bshd_strides(q, "q", qs);
   bshd_strides(out, "out", os);
+  // k_new / v_new / pos (MXFP8 cache only): the new tokens' rows [B, T, Hkv, D] are quantized into cache rows
+  // pos[b] + t as kv_cache_write would, then attended over -- one launch where the MFMA KV8 kernel covers the
+  // call (its append form), else the kv_write_mx8 launch followed by the call as it is without them
+  bool append = k_new.has_value();
+  TORCH_CHECK(append == v_new.has_value() && append == pos.has_value(), "decode_attn: k_new, v_new and pos go together");
+  TORCH_CHECK(!append || k_scale.has_value(), "decode_attn: k_new / v_new / pos need an MXFP8 cache (k_scale / v_scale)");
+  int64_t ns[3] = {0, 0, 0};
+  if (append) {
+    int64_t vs[3];
+    bshd_strides(*k_new, "k_new", ns);
+    bshd_strides(*v_new, "v_new", vs);
+    TORCH_CHECK(k_new->sizes() == v_new->sizes() && ns[0] == vs[0] && ns[1] == vs[1] && ns[2] == vs[2],
+                "decode_attn: k_new / v_new layouts must match");
+    TORCH_CHECK(k_new->size(0) == q.size(0) && k_new->size(1) == q.size(1) && k_new->size(2) == kc.size(1) &&
+                    k_new->size(3) == kc.size(3) && k_new->device() == q.device(),
+                "decode_attn: k_new / v_new must be [B, T, Hkv, D] of the call");
+    TORCH_CHECK(pos->scalar_type() == at::kInt && pos->numel() == q.size(0) && pos->is_contiguous() && pos->device() == q.device(),
+                "decode_attn: pos must be int32 [B]");
+  }
   // MXFP8 cache: the KV8 form of the MFMA kernel when it covers the call (M <= 16, D 64 / 128, contiguous
   // 16-byte aligned caches); otherwise both caches are dequantized into scratch bf16 caches and
   // the bf16 kernels run on those -- static shapes, capturable, slower
@@ -663,12 +686,22 @@ void decode_attn(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional<at::T
       a.ksc = ksc->data_ptr(); a.vsc = vsc->data_ptr();
       a.s_sb = ksc->stride(0); a.s_sh = ksc->stride(1); a.s_sl = ksc->stride(2);
     }
+    if (kv8 && append) {
+      a.k_new = k_new->data_ptr(); a.v_new = v_new->data_ptr(); a.pos0 = pos->data_ptr<int>();
+      a.n_sb = ns[0]; a.n_st = ns[1]; a.n_sh = ns[2];
+      a.Lcap = Lmax;
+    }
     // split counters of the chunk kernel, which never reads an MXFP8 cache
     int* counters = kv8 ? nullptr : decode_counters(q.device().index(), (int64_t)B * Hkv);
     return nxd::decode_attn_launch(a, (int)nsplit, counters);
   };
   const char* what = "decode_attn (mxfp8)";
   int rc = covered ? run(kc, vc, &*k_scale, &*v_scale) : -4;
+  if (rc == -4 && append) {   // no append form for this call: the write launch, then the call without the new rows
+    kv_cache_write(*k_new, *v_new, kc, vc, cache_idx, *pos, k_scale, v_scale);
+    append = false;
+    rc = covered ? run(kc, vc, &*k_scale, &*v_scale) : -4;
+  }
   if (rc == -4) {
     if (k_scale.has_value()) {   // not covered, misaligned rows, or the MFMA kernel is switched off
       kc = mx8_dequant(kc, *k_scale);
@@ -1291,35 +1324,38 @@ void dgemv(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, double e
   int64_t c_sb = 0, c_sh = 0, c_sl = 0;
   int Lmax = 0, max_pos = 0;
   if (epi == 3) {
-    TORCH_CHECK(cos_t.has_value() && sin_t.has_value() && pos.has_value() && kc.has_value() && vc.has_value(),
-                "dgemv rope_kv: cos, sin, pos, k/v cache required");
+    // kc and vc both absent: no cache write (null pointers, Lmax = 0: the kernels guard every cache store with
+    // 0 <= pos < Lmax); the rotated k and the v rows are in y either way
+    TORCH_CHECK(cos_t.has_value() && sin_t.has_value() && pos.has_value() && kc.has_value() == vc.has_value(),
+                "dgemv rope_kv: cos, sin, pos required, k/v cache both or neither");
     TORCH_CHECK(D % 2 == 0 && D >= 2 && nq >= 1 && nkv >= 1 && N == (nq + 2 * nkv) * D, "dgemv rope_kv: head layout");
     TORCH_CHECK(cos_t->scalar_type() == at::kFloat && sin_t->scalar_type() == at::kFloat && cos_t->is_contiguous() &&
                     sin_t->is_contiguous() && cos_t->dim() == 2 && cos_t->size(1) == D / 2 && sin_t->sizes() == cos_t->sizes(),
                 "dgemv rope_kv: fp32 cos/sin tables [P, D/2]");
     TORCH_CHECK(pos->scalar_type() == at::kLong && pos->is_contiguous() && pos->numel() == M, "dgemv rope_kv: int64 pos [M]");
-    check_bf16(*kc, "k_cache");
-    check_bf16(*vc, "v_cache");
-    TORCH_CHECK(kc->dim() == 4 && kc->sizes() == vc->sizes() && kc->strides() == vc->strides() && kc->stride(3) == 1 &&
-                    kc->size(1) == nkv && kc->size(3) == D,
-                "dgemv rope_kv: caches [B, Hkv, Lmax, D]");
     TORCH_CHECK(T >= 1 && M % T == 0, "dgemv rope_kv: rows must be whole sequences of T tokens");
     if (cache_idx.has_value()) {
       TORCH_CHECK(cache_idx->scalar_type() == at::kInt && cache_idx->is_contiguous() && cache_idx->numel() == M / T,
                   "dgemv rope_kv: int32 cache_idx [B]");
       ci = cache_idx->data_ptr<int>();
-    } else {
-      TORCH_CHECK(kc->size(0) >= M / T, "dgemv rope_kv: cache batch");
+    }
+    if (kc.has_value()) {
+      check_bf16(*kc, "k_cache");
+      check_bf16(*vc, "v_cache");
+      TORCH_CHECK(kc->dim() == 4 && kc->sizes() == vc->sizes() && kc->strides() == vc->strides() && kc->stride(3) == 1 &&
+                      kc->size(1) == nkv && kc->size(3) == D,
+                  "dgemv rope_kv: caches [B, Hkv, Lmax, D]");
+      TORCH_CHECK(cache_idx.has_value() || kc->size(0) >= M / T, "dgemv rope_kv: cache batch");
+      kp = kc->data_ptr();
+      vp = vc->data_ptr();
+      c_sb = kc->stride(0);
+      c_sh = kc->stride(1);
+      c_sl = kc->stride(2);
+      Lmax = kc->size(2);
     }
     cp = cos_t->data_ptr<float>();
     sp = sin_t->data_ptr<float>();
     pp = pos->data_ptr<int64_t>();
-    kp = kc->data_ptr();
-    vp = vc->data_ptr();
-    c_sb = kc->stride(0);
-    c_sh = kc->stride(1);
-    c_sl = kc->stride(2);
-    Lmax = kc->size(2);
     max_pos = cos_t->size(0);
   } else {
     TORCH_CHECK(epi >= 0 && epi <= 2, "dgemv: epi must be 0..3");
@@ -1405,29 +1441,31 @@ void dgemv_mx(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, doubl
   TORCH_CHECK(cfg == 0 || (cfg >= 17 && cfg <= 68), "dgemv_mx: cfg = 16 R + KS (4-16 rows: 16 T + KS)");
   const nxd::DgemvMxRope* rp = nullptr;
   if (epi == 3) {
-    TORCH_CHECK(cos_t.has_value() && sin_t.has_value() && pos.has_value() && kc.has_value() && vc.has_value(),
-                "dgemv_mx rope_kv: cos, sin, pos, k/v cache required");
+    // kc and vc both absent: no cache write (null pointers, Lmax = 0), as dgemv
+    TORCH_CHECK(cos_t.has_value() && sin_t.has_value() && pos.has_value() && kc.has_value() == vc.has_value(),
+                "dgemv_mx rope_kv: cos, sin, pos required, k/v cache both or neither");
     TORCH_CHECK(D % 2 == 0 && D >= 2 && nq >= 1 && nkv >= 1 && N == (nq + 2 * nkv) * D, "dgemv_mx rope_kv: head layout");
     TORCH_CHECK(cos_t->scalar_type() == at::kFloat && sin_t->scalar_type() == at::kFloat && cos_t->is_contiguous() &&
                     sin_t->is_contiguous() && cos_t->dim() == 2 && cos_t->size(0) >= 1 && cos_t->size(1) == D / 2 &&
                     sin_t->sizes() == cos_t->sizes(),
                 "dgemv_mx rope_kv: fp32 cos/sin tables [P, D/2]");
     TORCH_CHECK(pos->scalar_type() == at::kLong && pos->is_contiguous() && pos->numel() == M, "dgemv_mx rope_kv: int64 pos [M]");
-    check_bf16(*kc, "k_cache");
-    check_bf16(*vc, "v_cache");
-    TORCH_CHECK(kc->dim() == 4 && kc->sizes() == vc->sizes() && kc->strides() == vc->strides() && kc->stride(3) == 1 &&
-                    kc->size(1) == nkv && kc->size(3) == D,
-                "dgemv_mx rope_kv: caches [B, Hkv, Lmax, D]");
     TORCH_CHECK(T >= 1 && M % T == 0, "dgemv_mx rope_kv: rows must be whole sequences of T tokens");
     if (cache_idx.has_value()) {
       TORCH_CHECK(cache_idx->scalar_type() == at::kInt && cache_idx->is_contiguous() && cache_idx->numel() == M / T,
                   "dgemv_mx rope_kv: int32 cache_idx [B]");
       rope.cache_idx = cache_idx->data_ptr<int>();
-    } else {
-      TORCH_CHECK(kc->size(0) >= M / T, "dgemv_mx rope_kv: cache batch");
+    }
+    if (kc.has_value()) {
+      check_bf16(*kc, "k_cache");
+      check_bf16(*vc, "v_cache");
+      TORCH_CHECK(kc->dim() == 4 && kc->sizes() == vc->sizes() && kc->strides() == vc->strides() && kc->stride(3) == 1 &&
+                      kc->size(1) == nkv && kc->size(3) == D,
+                  "dgemv_mx rope_kv: caches [B, Hkv, Lmax, D]");
+      TORCH_CHECK(cache_idx.has_value() || kc->size(0) >= M / T, "dgemv_mx rope_kv: cache batch");
     }
     TORCH_CHECK(cos_t->device() == w.device() && sin_t->device() == w.device() && pos->device() == w.device() &&
-                    kc->device() == w.device() && vc->device() == w.device() &&
+                    (!kc.has_value() || (kc->device() == w.device() && vc->device() == w.device())) &&
                     (!cache_idx.has_value() || cache_idx->device() == w.device()),
                 "dgemv_mx rope_kv: operands on different devices");
     rope.nq = (int)nq, rope.nkv = (int)nkv, rope.D = (int)D;
@@ -1435,10 +1473,12 @@ void dgemv_mx(int64_t epi, at::Tensor x, c10::optional<at::Tensor> norm_w, doubl
     rope.sin_t = sin_t->data_ptr<float>();
     rope.pos = pos->data_ptr<int64_t>();
     rope.T = (int)T;
-    rope.kc = kc->data_ptr();
-    rope.vc = vc->data_ptr();
-    rope.c_sb = kc->stride(0), rope.c_sh = kc->stride(1), rope.c_sl = kc->stride(2);
-    rope.Lmax = (int)kc->size(2);
+    if (kc.has_value()) {
+      rope.kc = kc->data_ptr();
+      rope.vc = vc->data_ptr();
+      rope.c_sb = kc->stride(0), rope.c_sh = kc->stride(1), rope.c_sl = kc->stride(2);
+      rope.Lmax = (int)kc->size(2);
+    }
     rope.max_pos = (int)cos_t->size(0);
     rp = &rope;
   }
@@ -1604,7 +1644,8 @@ PYBIND11_MODULE(_C, m) {
   // window: sliding-window attention, a query sees itself and the window - 1 keys before it (0 = none)
   m.def("decode_attn", &decode_attn, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cache_idx"),
         py::arg("seq_len"), py::arg("out"), py::arg("scale"), py::arg("nsplit"), py::arg("window") = 0,
-        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
+        py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none(), py::arg("k_new") = py::none(),
+        py::arg("v_new") = py::none(), py::arg("pos") = py::none());
   m.def("decode_attn_oproj", &decode_attn_oproj, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("cache_idx"),
         py::arg("seq_len"), py::arg("wo"), py::arg("oacc"), py::arg("scale"), py::arg("window") = 0);
   m.def("decode_attn_sync_error", [](bool reset) { return nxd::decode_attn_sync_error(reset); }, py::arg("reset") = false);

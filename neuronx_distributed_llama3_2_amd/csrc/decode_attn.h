@@ -33,6 +33,15 @@ struct DecodeAttnArgs {
   float scale;                   // softmax scale
   int window;                    // sliding window in keys; 0: none
   hipStream_t stream;
+  // Append form (MXFP8 cache, MFMA kernel only): the new tokens' bf16 K / V rows [B, T, Hkv, D] (views of
+  // the QKV buffer: unit stride on D, 16-byte aligned rows, one set of element strides for both), which
+  // the launch quantizes into cache rows pos0[b] + t (rows outside [0, Lcap) dropped, as kv_cache_write)
+  // and attends over as if they were already there.  All null / 0: the cache is read as it is.
+  const void* k_new;
+  const void* v_new;
+  int64_t n_sb, n_st, n_sh;
+  const int* pos0;               // [B] cache position of token 0
+  int Lcap;                      // cache capacity in keys (Lmax may be rounded up to the partials' splits)
 };
 
 // What the fused attention + o_proj launch needs beside it
@@ -53,7 +62,8 @@ struct DecodeOprojArgs {
 // counters: zeroed [B * Hkv] ints of the chunk kernel's fused merge (null with an MXFP8 cache).
 int decode_attn_launch(DecodeAttnArgs a, int nsplit, int* counters);
 // MFMA flash-decoding kernel (decode_attn.hip); *nsplit_out > 1: the caller merges the partials.
-// Consumes the ranges armed by decode_attn_set_prefetch.
+// Consumes the ranges armed by decode_attn_set_prefetch.  With a.k_new (append form) anything but an
+// MXFP8 cache it covers is -1: the caller writes the rows itself (kv_write_mx8_launch) and calls again without.
 int decode_attn2_launch(DecodeAttnArgs a, int* nsplit_out);
 // Fused attention + o_proj (decode_attn.hip): a.out unused, bf16 cache only.
 int decode_attn_oproj_launch(DecodeAttnArgs a, const DecodeOprojArgs& o);

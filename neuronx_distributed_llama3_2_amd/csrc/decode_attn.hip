@@ -27,6 +27,7 @@
 // the residual stream with the rounding of the unfused o_proj epilogue and zeroes it.
 #include "common.h"
 #include "decode_attn.h"
+#include "kv_mx8.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -38,7 +39,7 @@ constexpr int KB = 64;            // keys per chunk (one wave)
 constexpr int KPS = 1024;         // most keys per workgroup split (one pass of 8 waves x 2 chunks)
 
 // Kernel variants: bits of attn_kernel's flags argument (their meaning is told at the kernel)
-enum : unsigned { FUSE = 1, WO_EARLY = 2, SYNC = 4, WIN = 8, KV8 = 16 };
+enum : unsigned { FUSE = 1, WO_EARLY = 2, SYNC = 4, WIN = 8, KV8 = 16, APP = 32 };
 // D = 64: 8 waves (<= 2 chunks each per 1024-key split); D = 128: 4 waves (LDS: V tiles + merge)
 constexpr int waves(int D) { return D == 64 ? 8 : 4; }
 // dynamic LDS of attn_kernel: a V tile per wave, then the waves' O rows and (max, sum) for the merge
@@ -95,6 +96,13 @@ struct Params {
   const uint8_t* ksc;
   const uint8_t* vsc;
   int64_t s_sb, s_sh, s_sl;
+  // APP (with KV8): the new tokens' bf16 rows [B, T, Hkv, D] (element strides n_*), the cache position of
+  // token 0 of each sequence and the cache capacity; kc / vc / ksc / vsc are then written as well
+  const uint16_t* k_new;
+  const uint16_t* v_new;
+  int64_t n_sb, n_st, n_sh;
+  const int* pos0;
+  int Lcap;
 };
 static_assert(std::is_trivially_copyable<Params>::value && sizeof(Params) <= 4096, "kernel-argument struct");
 
@@ -193,13 +201,26 @@ __device__ __forceinline__ void oproj_tail(const Params& p, const float* of, con
 // into the same bf16 LDS tile, so the transposed reads, the softmax, P.V and the merge see the values a
 // bf16 cache holding the dequantized data would give them, in the same order: the outputs are equal
 // bit for bit.
+// APP (with KV8, never FUSE): the quantizing cache append in the same launch -- what kv_write_mx8 followed by
+// the KV8 kernel computes, output bits and cache bytes, without the write launch.  The new tokens' bf16
+// rows k_new / v_new [B, T, Hkv, D] belong at cache rows pos0[b] + t.
+//   write: the split-0 workgroup of a (batch, kv head) quantizes that head's 2 * T * D / 32 blocks, one per
+//          thread (kv_write_mx8's code: kv_mx8.h), and stores codes and scale bytes; rows outside the cache
+//          are dropped.
+//   read:  no wave reads those bytes.  A chunk that holds new rows (wave-uniform test) takes them from
+//          k_new / v_new: the lane loads the bf16 of its fragment, the block's amax goes over the lanes that
+//          share the block -- the four g lanes of a key for K (8 elements each), lane ^ 1 for V (16 each) --
+//          and the lane quantizes into kf8 / ksb and vv / vsb, the registers a load of the written bytes
+//          would have filled.  So no ordering between the write and any read is needed, inside a workgroup
+//          or between splits, and from there on this is the KV8 kernel.
 // F: the variant's flags.  WO_EARLY (with FUSE) issues the Wo block before the K / V loads (WO_LATE below
 // is its absence, the default).
 template <int D, unsigned F>
 __global__ void __launch_bounds__(64 * waves(D)) attn_kernel(Params p) {
   constexpr int NWV = waves(D);
   constexpr bool FUSE = (F & dattn::FUSE) != 0, WO_LATE = (F & dattn::WO_EARLY) == 0, SYNC = (F & dattn::SYNC) != 0;
-  constexpr bool WIN = (F & dattn::WIN) != 0, KV8 = (F & dattn::KV8) != 0;
+  constexpr bool WIN = (F & dattn::WIN) != 0, KV8 = (F & dattn::KV8) != 0, APP = (F & dattn::APP) != 0;
+  static_assert(!APP || (KV8 && !FUSE), "the append form quantizes into an MXFP8 cache, never fused with o_proj");
   static_assert(FUSE || WO_LATE, "WO_EARLY is a FUSE form");
   static_assert(!SYNC || FUSE, "SYNC is a FUSE form");
   static_assert(!WIN || !SYNC, "no SYNC form with a sliding window");
@@ -273,7 +294,92 @@ __global__ void __launch_bounds__(64 * waves(D)) attn_kernel(Params p) {
   const uint8_t* vbase8 = reinterpret_cast<const uint8_t*>(p.vc) + (int64_t)cb * p.c_sb + (int64_t)hkv * p.c_sh;
   const uint8_t* ksbase = p.ksc + (int64_t)cb * p.s_sb + (int64_t)hkv * p.s_sh;
   const uint8_t* vsbase = p.vsc + (int64_t)cb * p.s_sb + (int64_t)hkv * p.s_sh;
+  // APP: cache rows [p0, p0 + T) are the new tokens', read from the head's k_new / v_new rows
+  const int64_t p0 = APP ? p.pos0[b] : 0;
+  const uint16_t* knew = APP ? p.k_new + (int64_t)b * p.n_sb + (int64_t)hkv * p.n_sh : nullptr;
+  const uint16_t* vnew = APP ? p.v_new + (int64_t)b * p.n_sb + (int64_t)hkv * p.n_sh : nullptr;
+  // load_chunk for a chunk that holds new rows: a lane whose row is new loads bf16 and quantizes (the
+  // shuffles run on every lane: the lanes of a block share the row, so all of them are new or none is).
+  // Two rounds of loads, each issued whole before its first use -- the cache loads of the other lanes and the
+  // new K rows, then the new V rows into the same registers -- so the chunk costs one round trip to k_new /
+  // v_new (L2: the QKV launch just wrote them) more than a chunk of cached rows, not one per fragment.
+  auto load_chunk_new = [&](int k0) {
+    if constexpr (APP) {
+      const auto new_row = [&](int key) { return (int64_t)min(k0 + key, slen - 1) - p0; };   // token, if in [0, T)
+      u32x4_t x[D / 8];
+#pragma unroll
+      for (int i = 0; i < VL8; ++i) {
+        const int idx = lane + 64 * i, key = idx / (D / 16), c = idx % (D / 16);
+        const int64_t t = new_row(key), row = t + p0;
+        if (t < 0 || t >= p.T) {
+          vv[i] = *reinterpret_cast<const u32x4_t*>(vbase8 + row * p.c_sl + 16 * c);
+          vsb[i] = vsbase[row * p.s_sl + c / 2];
+        }
+      }
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        const int64_t t = new_row(kt * 16 + mi), row = t + p0;
+        if (t >= 0 && t < p.T) {
+#pragma unroll
+          for (int s = 0; s < NS; ++s) x[kt * NS + s] = *reinterpret_cast<const u32x4_t*>(knew + t * p.n_st + 32 * s + 8 * g);
+        } else {
+          const uint8_t* kr = kbase8 + row * p.c_sl + 8 * g;
+#pragma unroll
+          for (int s = 0; s < NS; ++s) {
+            x[kt * NS + s] = u32x4_t{0, 0, 0, 0};
+            kf8[kt][s] = *reinterpret_cast<const u32x2_t*>(kr + 32 * s);
+          }
+          ksb[kt] = *reinterpret_cast<const kscale_t*>(ksbase + row * p.s_sl);
+        }
+      }
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        const int64_t t = new_row(kt * 16 + mi);
+        const bool nw = t >= 0 && t < p.T;
+        kscale_t sb = 0;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          uint32_t am = kvmx::amax8(x[kt * NS + s]);
+          am = max(am, (uint32_t)__shfl_xor((int)am, 16, 64));
+          am = max(am, (uint32_t)__shfl_xor((int)am, 32, 64));
+          const int e = kvmx::block_exp(am);
+          if (nw) kf8[kt][s] = kvmx::quant8(x[kt * NS + s], e);
+          sb |= (kscale_t)e << (8 * s);
+        }
+        if (nw) ksb[kt] = sb;
+      }
+#pragma unroll
+      for (int i = 0; i < VL8; ++i) {
+        const int idx = lane + 64 * i, key = idx / (D / 16), c = idx % (D / 16);
+        const int64_t t = new_row(key);
+        x[2 * i] = x[2 * i + 1] = u32x4_t{0, 0, 0, 0};
+        if (t >= 0 && t < p.T) {
+          const uint16_t* src = vnew + t * p.n_st + 16 * c;
+          x[2 * i] = *reinterpret_cast<const u32x4_t*>(src);
+          x[2 * i + 1] = *reinterpret_cast<const u32x4_t*>(src + 8);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < VL8; ++i) {
+        const int64_t t = new_row((lane + 64 * i) / (D / 16));
+        uint32_t am = max(kvmx::amax8(x[2 * i]), kvmx::amax8(x[2 * i + 1]));
+        am = max(am, (uint32_t)__shfl_xor((int)am, 1, 64));
+        if (t >= 0 && t < p.T) {
+          const int e = kvmx::block_exp(am);
+          const u32x2_t c0 = kvmx::quant8(x[2 * i], e), c1 = kvmx::quant8(x[2 * i + 1], e);
+          vv[i] = u32x4_t{c0[0], c0[1], c1[0], c1[1]};
+          vsb[i] = (uint8_t)e;
+        }
+      }
+    }
+  };
   auto load_chunk = [&](int k0) {
+    if constexpr (APP) {
+      if (k0 < p0 + p.T && k0 + KB > p0) {   // wave-uniform
+        load_chunk_new(k0);
+        return;
+      }
+    }
     if constexpr (KV8) {
 #pragma unroll
       for (int i = 0; i < VL8; ++i) {
@@ -306,6 +412,24 @@ __global__ void __launch_bounds__(64 * waves(D)) attn_kernel(Params p) {
   };
   int k0 = kbeg + split * p.kps + wid * KB;
   if (k0 < kend) load_chunk(k0);
+  if constexpr (APP) {
+    // the append: thread (k | v, token t, block j) of the split-0 workgroup quantizes one block of this head
+    const int nblk = p.T * NS, i = tid < nblk ? tid : tid - nblk, t = i / NS, j = i % NS;
+    const bool is_v = tid >= nblk;
+    const int64_t ps = p0 + t;
+    if (split == 0 && tid < 2 * nblk && ps >= 0 && ps < p.Lcap) {
+      const uint16_t* src = (is_v ? vnew : knew) + t * p.n_st + 32 * j;
+      u32x4_t x[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) x[q] = *reinterpret_cast<const u32x4_t*>(src + 8 * q);
+      const int e = kvmx::block_exp(max(max(kvmx::amax8(x[0]), kvmx::amax8(x[1])), max(kvmx::amax8(x[2]), kvmx::amax8(x[3]))));
+      const u32x2_t c0 = kvmx::quant8(x[0], e), c1 = kvmx::quant8(x[1], e), c2 = kvmx::quant8(x[2], e), c3 = kvmx::quant8(x[3], e);
+      uint8_t* dst = const_cast<uint8_t*>(is_v ? vbase8 : kbase8) + ps * p.c_sl + 32 * j;
+      *reinterpret_cast<u32x4_t*>(dst) = u32x4_t{c0[0], c0[1], c1[0], c1[1]};
+      *reinterpret_cast<u32x4_t*>(dst + 16) = u32x4_t{c2[0], c2[1], c3[0], c3[1]};
+      const_cast<uint8_t*>(is_v ? vsbase : ksbase)[ps * p.s_sl + j] = (uint8_t)e;
+    }
+  }
   // FUSE: the Wo block is issued AFTER the q and first K / V loads.  vmcnt retires in issue order:
   // issued first (round 3), the cold-HBM Wo loads had to land before the first score MFMA could
   // read its L2-resident K fragments, so their latency was added to the attention instead of
@@ -725,6 +849,8 @@ static Params make_params(const DecodeAttnArgs& a) {
   p.c_sb = a.c_sb; p.c_sh = a.c_sh; p.c_sl = a.c_sl;
   p.ksc = (const uint8_t*)a.ksc; p.vsc = (const uint8_t*)a.vsc;
   p.s_sb = a.s_sb; p.s_sh = a.s_sh; p.s_sl = a.s_sl;
+  p.k_new = (const uint16_t*)a.k_new; p.v_new = (const uint16_t*)a.v_new;
+  p.n_sb = a.n_sb; p.n_st = a.n_st; p.n_sh = a.n_sh; p.pos0 = a.pos0; p.Lcap = a.Lcap;
   p.cache_idx = a.cache_idx; p.seq_len = a.seq_len;
   p.out = (uint16_t*)a.out; p.o_sb = a.o_sb; p.o_st = a.o_st; p.o_sh = a.o_sh;
   p.po = a.po; p.pm = a.pm; p.pl = a.pl;
@@ -780,6 +906,15 @@ int decode_attn2_launch(DecodeAttnArgs a, int* nsplit_out) {
         a.s_sb % sb || a.s_sh % sb || a.s_sl % sb)
       return -1;
   }
+  // append form (a.k_new ...): only with an MXFP8 cache, the new rows 16-byte aligned, and a capacity that
+  // bounds the write (at most what the strides span)
+  const bool app = a.k_new != nullptr || a.v_new != nullptr || a.pos0 != nullptr;
+  if (app) {
+    const auto al16 = [](const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; };
+    if (!kv8 || !a.k_new || !a.v_new || !a.pos0 || !al16(a.k_new) || !al16(a.v_new) || a.n_sb % 8 || a.n_st % 8 || a.n_sh % 8 ||
+        a.Lcap <= 0 || a.Lcap > a.Lmax)
+      return -1;
+  }
   const int Leff = window_span(a.Lmax, a.T, a.window);
   Params p = make_params(a);
   p.kps = keys_per_split(Leff, a.B, a.Hkv);
@@ -797,6 +932,8 @@ int decode_attn2_launch(DecodeAttnArgs a, int* nsplit_out) {
   g_pf[0] = g_pf[1] = nullptr;
   g_pf_bytes[0] = g_pf_bytes[1] = 0;
   const dim3 grid(p.attn_wgs + pf_wgs);
+  if (app)   // ... with the quantizing append
+    return a.window ? launch_attn<WIN | KV8 | APP>(D, grid, a.stream, p) : launch_attn<KV8 | APP>(D, grid, a.stream, p);
   if (kv8)   // MXFP8 cache: the KV8 instantiations (same LDS as the bf16 ones)
     return a.window ? launch_attn<WIN | KV8>(D, grid, a.stream, p) : launch_attn<KV8>(D, grid, a.stream, p);
   return a.window ? launch_attn<WIN>(D, grid, a.stream, p) : launch_attn<0>(D, grid, a.stream, p);

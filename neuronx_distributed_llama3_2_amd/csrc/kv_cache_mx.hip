@@ -19,26 +19,10 @@
 // mx8_dequant: code * 2^(e-127) by v_cvt_scalef32_pk_bf16_fp8 (multiplies by the scale operand);
 // exact, every product has at most four significant bits.
 #include "common.h"
+#include "kv_mx8.h"   // cvt4_fp8, clamp_pair
 
 namespace nxd {
 namespace kvmx {
-
-typedef short short2_t __attribute__((ext_vector_type(2)));
-
-// 4 codes (one dword) from 4 bf16 (two dwords of pairs), divided by `scale`
-__device__ __forceinline__ uint32_t cvt4_fp8(uint32_t p01, uint32_t p23, float scale) {
-  short2_t r = {0, 0};
-  r = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(r, __builtin_bit_cast(bf16x2_t, p01), scale, false);
-  r = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(r, __builtin_bit_cast(bf16x2_t, p23), scale, true);
-  return __builtin_bit_cast(uint32_t, r);
-}
-
-// both halves of a bf16 pair clamped in magnitude to `lim` (bf16 bits, sign clear)
-__device__ __forceinline__ uint32_t clamp_pair(uint32_t p, uint32_t lim) {
-  const uint32_t lo = min(p & 0x7fffu, lim) | (p & 0x8000u);
-  const uint32_t hi = min((p >> 16) & 0x7fffu, lim) | ((p >> 16) & 0x8000u);
-  return lo | (hi << 16);
-}
 
 __global__ void __launch_bounds__(256) kv_write_mx8_kernel(const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
                                                            int64_t n_sb, int64_t n_st, int64_t n_sh,

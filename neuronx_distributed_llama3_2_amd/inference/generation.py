@@ -317,6 +317,7 @@ class LlamaForCausalLMInference:
         whether the model can take the fused path."""
         self.model._decode_fused_ok = None if enabled else False
         self.model._decode_fused_mx_ok = None if enabled else False   # the MXFP4 form of the same launches
+        self.model._decode_fused_kv8_ok = None if enabled else ""     # ... and their route over an MXFP8 cache
 
     def _context_encode(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                         position_ids: Optional[torch.Tensor] = None, seq_ids: Optional[torch.Tensor] = None) -> torch.Tensor:

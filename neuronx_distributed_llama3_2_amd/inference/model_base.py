@@ -16,7 +16,9 @@ RoPE + KV-cache write after QKV, residual adds after o_proj / down -- so a layer
 (QKV, attention, o_proj, gate_up, down) instead of 10 (`NXD_DECODE_FUSED=0` disables it).
 
 KV cache: ONE allocation [layers, 2, max_batch, kv_heads_local, max_len, head_dim] (bf16);
-`seq_ids` selects cache rows (continuous batching).
+`seq_ids` selects cache rows (continuous batching).  With an MXFP8 cache (`kv_cache_dtype="mxfp8"`, TP = 1,
+head dim 64 / 128) the fast path is the same five launches: the QKV launch writes no cache and the attention
+launch quantizes and appends the new rows itself (`_decode_fusable_kv8`, `NXD_DECODE_FUSED_KV8=0` disables it).
 
 Sliding window (`config.sliding_window`, Mistral / Mixtral): prefill masks with the interval-masked
 flash attention (`ops.ranges_sliding_window`), decode passes the window to the decode attention
@@ -66,6 +68,11 @@ _EMB_FUSED = os.environ.get("NXD_DECODE_EMB_FUSED", "1") == "1"
 # (Measured performance, fused MXFP4 decode).  NXD_DECODE_FUSED_MX_ROWS (ops/gemv.py), read at the same
 # point, extends the route to 4-8 rows on csrc/decode_fused_mx_mfma.hip (_decode_fusable_mx_rows).
 _FUSED_MX_DEFAULT = "1"
+# NXD_DECODE_FUSED_KV8: a model with an MXFP8 KV cache decodes on the same fused launches (bf16 or MXFP4
+# weights), the QKV launch writing no cache and the attention launch appending the quantized rows itself
+# (ops/decode.py, quantizing append).  "0": the unfused launches, as before.  Read when a model is first
+# checked (_check_decode_fusable_kv8); the default is justified in the README (MXFP8 KV cache, fused decode).
+_FUSED_KV8_DEFAULT = "1"
 
 
 class DecoderInferenceMixin:
@@ -106,6 +113,7 @@ class DecoderInferenceMixin:
                                               device=device) if quant else None
             self._decode_fused_ok = None   # the fused decode launches read and write a bf16 cache
             self._decode_fused_mx_ok = None
+            self._decode_fused_kv8_ok = None
         return self.kv_cache
 
     def reset_kv_cache(self) -> None:
@@ -170,6 +178,10 @@ class DecoderInferenceMixin:
             return self._forward_decode_fused(input_ids, positions, seq_ids, cache_len, last_index, return_hidden)
         if not prefill and (self._decode_fusable_mx(input_ids) or self._decode_fusable_mx_rows(input_ids)):
             return self._forward_decode_fused_mx(input_ids, positions, seq_ids, cache_len, last_index, return_hidden)
+        kv8 = "" if prefill else self._decode_fusable_kv8(input_ids)
+        if kv8:   # MXFP8 cache: the same launches, the cache append inside the attention launch
+            fwd = self._forward_decode_fused if kv8 == "bf16" else self._forward_decode_fused_mx
+            return fwd(input_ids, positions, seq_ids, cache_len, last_index, return_hidden)
         nq, nkv, D = self.nq, self.nkv, self.head_dim
         W = (nq + 2 * nkv) * D
         cos_t, sin_t = self.model.rope_cache.tables(input_ids.device)
@@ -221,12 +233,14 @@ class DecoderInferenceMixin:
         M = input_ids.numel()
         return ok and input_ids.is_cuda and M <= 8 and M * self.config.hidden_size <= 32768
 
-    def _check_decode_fusable(self) -> bool:
+    def _check_decode_fusable(self, kv8: bool = False) -> bool:
+        """kv8: the checks of the MXFP8-cache route (_check_decode_fusable_kv8), which lifts the cache condition."""
         if os.environ.get("NXD_DECODE_FUSED", "1") == "0":
             return False
-        if self._kv_quantized():
+        if self._kv_quantized() and not kv8:
             # the fused QKV epilogue writes bf16 cache elements (one output row per wave) and the fused
-            # attention + o_proj reads bf16: an MXFP8 cache decodes on the unfused launches
+            # attention + o_proj reads bf16: an MXFP8 cache decodes on the unfused launches, or on the
+            # route of _decode_fusable_kv8
             return False
         if self.tp > 1 and os.environ.get("NXD_DECODE_FUSED_TP", "1") == "0":
             return False
@@ -244,6 +258,37 @@ class DecoderInferenceMixin:
                 return False
         lm = self.lm_head.weight
         return lm.dtype == torch.bfloat16 and getattr(self.lm_head, "bias", None) is None
+
+    def _decode_fusable_kv8(self, input_ids: torch.Tensor) -> str:
+        """The gate of the fused decode route over an MXFP8 KV cache: "bf16" (_forward_decode_fused) or "mx"
+        (_forward_decode_fused_mx) when this step takes it, else "".  The step's query group must fit the
+        MFMA attention kernel ((nq / nkv) * T <= 16), its rows the limits of the gates beside this one."""
+        ok = getattr(self, "_decode_fused_kv8_ok", None)
+        if ok is None:
+            ok = self._decode_fused_kv8_ok = self._check_decode_fusable_kv8()
+        if not ok or not input_ids.is_cuda or (self.nq // self.nkv) * input_ids.shape[1] > 16:
+            return ""
+        M, H = input_ids.numel(), self.config.hidden_size
+        if ok == "bf16":
+            return ok if M <= 8 and M * H <= 32768 else ""
+        if M <= MX_DECODE_MAX_ROWS and mx_route(M) == "gemv" and M * H <= 32768:   # _decode_fusable_mx
+            return ok
+        rows = getattr(self, "_decode_fused_mx_rows", 0)                            # _decode_fusable_mx_rows
+        if self._decode_fused_mx_qkv:
+            return ok if (self.head_dim // 2) % 16 == 0 and mx_decode_mfma_ok(M, min(rows, 16)) else ""
+        return ok if M <= 8 and M * H <= 32768 and mx_decode_mfma_ok(M, rows) else ""
+
+    def _check_decode_fusable_kv8(self) -> str:
+        """Which fused decode route an MXFP8-cache model takes: the checks of _check_decode_fusable ("bf16") or
+        _check_decode_fusable_mx ("mx") without their cache condition, at TP = 1 and head dim 64 / 128 (the
+        MFMA attention kernel's), unless NXD_DECODE_FUSED_KV8 (default: _FUSED_KV8_DEFAULT) is 0."""
+        if not self._kv_quantized() or self.tp > 1 or self.head_dim not in (64, 128):
+            return ""
+        if os.environ.get("NXD_DECODE_FUSED_KV8", _FUSED_KV8_DEFAULT) == "0":
+            return ""
+        if self._check_decode_fusable(kv8=True):
+            return "bf16"
+        return "mx" if self._check_decode_fusable_mx(kv8=True) else ""
 
     def _decode_oacc(self, M: int, res: torch.Tensor) -> torch.Tensor:
         """fp32 [8, H] o_proj accumulator of the fused attention + o_proj decode launch: zero between
@@ -276,25 +321,31 @@ class DecoderInferenceMixin:
         qkv = torch.empty((M, W), dtype=res.dtype, device=res.device)
         window = self._decode_window()
         win = (window,) if window else ()   # no window: the kernels' un-windowed arguments
+        # MXFP8 cache (_decode_fusable_kv8): the QKV launch gets no caches, the attention launch appends
+        kv8 = self._kv_quantized()
+        pos0 = positions[:, 0].to(torch.int32).contiguous() if kv8 else None
         for i, layer in enumerate(self.model.layers):
             attn = layer.self_attn
             w_qkv = attn.qkv_proj._fused_weight_bias()[0] if hasattr(attn.qkv_proj, "_fused_weight_bias") \
                 else attn.qkv_proj.weight
-            kc, vc = self.kv_cache[i, 0], self.kv_cache[i, 1]
+            kc, vc, sc = self._layer_cache(i)
+            qc = (None, None) if kv8 else (kc, vc)
             # RMSNorm -> QKV -> RoPE -> k/v into the cache, one launch (layer 0: + the embedding gather)
             if i == 0 and emb_fused:
                 C.dgemv(3, ew, layer.input_layernorm.weight, self.eps, w_qkv, qkv, nq, nkv, D, cos_t, sin_t, pos, T,
-                        kc, vc, sid32, xidx=ids, xcopy=res)
+                        *qc, sid32, xidx=ids, xcopy=res)
             else:
                 C.dgemv(3, res, layer.input_layernorm.weight, self.eps, w_qkv, qkv, nq, nkv, D, cos_t, sin_t, pos, T,
-                        kc, vc, sid32)
-            q = qkv.view(B, T, nq + 2 * nkv, D)[:, :, :nq]
+                        *qc, sid32)
+            qkv4 = qkv.view(B, T, nq + 2 * nkv, D)
+            q = qkv4[:, :, :nq]
+            app = dict(k_new=qkv4[:, :, nq:nq + nkv], v_new=qkv4[:, :, nq + nkv:], positions=pos0) if kv8 else {}
             ln2, w_gu, w_d = self._fused_ffn_weights(layer)
             if _PREFETCH_MB > 0:
                 # spare workgroups of the attention launch pull o_proj and the head of gate_up into
                 # the Infinity Cache while the (latency-bound) attention leaves HBM idle
                 C.decode_attn_prefetch(attn.o_proj.weight, -1, w_gu, int(_PREFETCH_MB * 2**20), _PREFETCH_WGS)
-            fuse_o = (_ATTN_OPROJ and _PREFETCH_MB <= 0 and B <= _ATTN_OPROJ_MAXB
+            fuse_o = (_ATTN_OPROJ and _PREFETCH_MB <= 0 and B <= _ATTN_OPROJ_MAXB and not kv8
                       and not getattr(self, "_decode_deterministic", False))
             oacc = self._decode_oacc(M, res) if fuse_o else None
             if oacc is not None and C.decode_attn_oproj(q, kc, vc, sid32, cache_len.to(torch.int32), attn.o_proj.weight,
@@ -305,7 +356,7 @@ class DecoderInferenceMixin:
                 C.dgemv(2, res, ln2, self.eps, w_gu, a, 0, 0, 0, None, None, None, 1, None, None, None, oacc, None)
                 C.dgemv(1, a, None, 0.0, w_d, res, 0, 0, 0, None, None, None, 1, None, None, None, None, oacc)
                 continue
-            o = ops.decode_attention(q, kc, vc, cache_len, sid32, window=window)
+            o = ops.decode_attention(q, kc, vc, cache_len, sid32, window=window, **sc, **app)
             C.dgemv(1, o.reshape(M, nq * D), None, 0.0, attn.o_proj.weight, res, 0, 0, 0, None, None, None, 1,
                     None, None, None)                                   # res += o_proj(o)
             a = torch.empty((M, w_d.shape[1]), dtype=res.dtype, device=res.device)
@@ -361,7 +412,7 @@ class DecoderInferenceMixin:
         return ok and input_ids.is_cuda and M <= 8 and M * self.config.hidden_size <= 32768 and \
             mx_decode_mfma_ok(M, rows)
 
-    def _check_decode_fusable_mx(self) -> bool:
+    def _check_decode_fusable_mx(self, kv8: bool = False) -> bool:
         """Whether a weight-quantized model decodes on the fused launches that read MXFP4
         (csrc/decode_fused_mx.hip): TP = 1, bf16 KV cache, bias-free QKV that is bf16 in every layer or packed
         MXFP4 in every layer (remembered in _decode_fused_mx_qkv; from 4 rows the packed form needs
@@ -372,7 +423,7 @@ class DecoderInferenceMixin:
         if os.environ.get("NXD_DECODE_FUSED", "1") == "0" or \
                 os.environ.get("NXD_DECODE_FUSED_MX", _FUSED_MX_DEFAULT) == "0":
             return False
-        if self.tp > 1 or self._kv_quantized():
+        if self.tp > 1 or (self._kv_quantized() and not kv8):   # kv8: _check_decode_fusable_kv8 lifts the cache condition
             return False
         if type(self)._qkv_hook is not DecoderInferenceMixin._qkv_hook or type(self)._norm is not DecoderInferenceMixin._norm:
             return False
@@ -422,25 +473,31 @@ class DecoderInferenceMixin:
             res = ops.vocab_parallel_embedding(input_ids, ew, emb.start_index).reshape(M, -1).contiguous()
         qkv = torch.empty((M, W), dtype=res.dtype, device=res.device)
         window = self._decode_window()
+        # MXFP8 cache (_decode_fusable_kv8): the QKV launch gets no caches, the attention launch appends
+        kv8 = self._kv_quantized()
+        pos0 = positions[:, 0].to(torch.int32).contiguous() if kv8 else None
         for i, layer in enumerate(self.model.layers):
             attn = layer.self_attn
             w_qkv = attn.qkv_proj._fused_weight_bias()[0] if hasattr(attn.qkv_proj, "_fused_weight_bias") \
                 else attn.qkv_proj.weight
-            kc, vc = self.kv_cache[i, 0], self.kv_cache[i, 1]
+            kc, vc, sc = self._layer_cache(i)
+            qc = (None, None) if kv8 else (kc, vc)
             if w_qkv.dtype == torch.uint8:   # packed QKV
                 gather = dict(xidx=ids, xcopy=res) if i == 0 and emb_fused else {}
                 C.dgemv_mx(3, ew if gather else res, layer.input_layernorm.weight, self.eps, w_qkv, attn.qkv_proj.scale, qkv,
-                           nq=nq, nkv=nkv, D=D, cos_t=cos_t, sin_t=sin_t, pos=pos, T=T, kc=kc, vc=vc, cache_idx=sid32,
+                           nq=nq, nkv=nkv, D=D, cos_t=cos_t, sin_t=sin_t, pos=pos, T=T, kc=qc[0], vc=qc[1], cache_idx=sid32,
                            **gather)
             elif i == 0 and emb_fused:
                 C.dgemv(3, ew, layer.input_layernorm.weight, self.eps, w_qkv, qkv, nq, nkv, D, cos_t, sin_t, pos, T,
-                        kc, vc, sid32, xidx=ids, xcopy=res)
+                        *qc, sid32, xidx=ids, xcopy=res)
             else:
                 C.dgemv(3, res, layer.input_layernorm.weight, self.eps, w_qkv, qkv, nq, nkv, D, cos_t, sin_t, pos, T,
-                        kc, vc, sid32)
-            q = qkv.view(B, T, nq + 2 * nkv, D)[:, :, :nq]
+                        *qc, sid32)
+            qkv4 = qkv.view(B, T, nq + 2 * nkv, D)
+            q = qkv4[:, :, :nq]
+            app = dict(k_new=qkv4[:, :, nq:nq + nkv], v_new=qkv4[:, :, nq + nkv:], positions=pos0) if kv8 else {}
             ln2, gu, dn = self._fused_mx_ffn_weights(layer)
-            o = ops.decode_attention(q, kc, vc, cache_len, sid32, window=window)
+            o = ops.decode_attention(q, kc, vc, cache_len, sid32, window=window, **sc, **app)
             C.dgemv_mx(1, o.reshape(M, nq * D), None, 0.0, attn.o_proj.weight, attn.o_proj.scale, res)   # res += o_proj(o)
             a = torch.empty((M, gu.weight.shape[0] // 2), dtype=res.dtype, device=res.device)
             C.dgemv_mx(2, res, ln2, self.eps, gu.weight, gu.scale, a)                                 # norm + SwiGLU

@@ -29,6 +29,18 @@ A zeroed cache (`reset_kv_cache`) is valid: code 0 is 0 under any scale.
 
 Every code times `2^(e-127)` has at most four significant bits, so dequantization to bf16 loses
 nothing: a decode step over a quantized cache equals the same step over its bf16 dequantization.
+
+Quantizing append in the attention launch (the APP form of csrc/decode_attn.hip)
+--------------------------------------------------------------------------------
+`decode_attention(..., k_scale=, v_scale=, k_new=, v_new=, positions=)` is, in output bits and in cache
+bytes, `kv_cache_write(k_new, v_new, ..., positions, cache_idx, k_scale=, v_scale=)` followed by
+`decode_attention(..., k_scale=, v_scale=)`, for any positions, seq_len, cache_idx, window and T.
+Where the MFMA kernel covers the call ((Hq / Hkv) * T <= 16, head dim 64 or 128, contiguous caches,
+16-byte aligned new rows with one set of strides) it is one launch: the split-0 workgroup of each
+(batch, kv head) quantizes and stores the new rows, and every wave that meets a new row takes it from
+`k_new` / `v_new` and quantizes it in registers, so nothing the launch writes is read in it.  Elsewhere
+(off the GPU, `NXD_FORCE_REFERENCE=1`, larger query groups, other head dims) it is the two calls.
+The fused decode step of an MXFP8-cache model uses it (inference/model_base.py, `NXD_DECODE_FUSED_KV8`).
 """
 
 from __future__ import annotations
@@ -109,24 +121,38 @@ def _mx8_caches(k_cache, v_cache, k_scale, v_scale) -> bool:
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, seq_len: torch.Tensor,
                      cache_idx: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None,
                      out: Optional[torch.Tensor] = None, window: Optional[int] = None,
-                     k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
+                     k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
+                     positions: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q: [B, T, Hq, D] new-token queries; keys [0, seq_len[b]) are valid for the LAST token, and
     token t sees keys < lim = seq_len[b] - (T - 1 - t).  window: sliding-window attention, token t
     sees only the keys >= lim - window (itself and the window - 1 before it); None, 0 or at least
     the cache length mean no window.  uint8 caches with k_scale / v_scale: an MXFP8 cache (module
-    docstring).  Returns [B, T, Hq, D]."""
+    docstring).  k_new / v_new [B, T, Hkv, D] with positions [B] (all three or none, MXFP8 cache only;
+    TypeError otherwise): the call first appends those rows as `kv_cache_write` would -- in the
+    attention launch itself where the MFMA kernel covers the call (module docstring).
+    Returns [B, T, Hq, D]."""
     B, T, Hq, D = q.shape
     quant = _mx8_caches(k_cache, v_cache, k_scale, v_scale)
+    append = k_new is not None
+    if (v_new is not None) != append or (positions is not None) != append:
+        raise TypeError("k_new, v_new and positions go together")
+    if append and not quant:
+        raise TypeError("k_new / v_new / positions append to an MXFP8 cache (uint8 codes with k_scale / v_scale)")
     window = decode_window(window, k_cache.shape[2])
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
     if out is None:
         out = torch.empty((B, T, Hq, D), dtype=q.dtype, device=q.device)
     if use_native(q, k_cache):
         nsplit = max(1, (k_cache.shape[2] + CHUNK - 1) // CHUNK)
+        kw = dict(k_scale=k_scale, v_scale=v_scale) if quant else {}
+        if append:
+            kw.update(k_new=k_new, v_new=v_new, pos=positions.to(torch.int32))
         ext().decode_attn(q, k_cache, v_cache, cache_idx.to(torch.int32) if cache_idx is not None else None,
-                          seq_len.to(torch.int32), out, float(scale), nsplit, *((window,) if window else ()),
-                          **(dict(k_scale=k_scale, v_scale=v_scale) if quant else {}))
+                          seq_len.to(torch.int32), out, float(scale), nsplit, *((window,) if window else ()), **kw)
         return out
+    if append:
+        kv_cache_write(k_new, v_new, k_cache, v_cache, positions, cache_idx, k_scale=k_scale, v_scale=v_scale)
     Hkv = k_cache.shape[1]
     g = Hq // Hkv
     for b in range(B):

@@ -7,6 +7,11 @@ launches) that cycle over enough layer caches to exceed the 256 MiB Infinity Cac
 streams its keys from HBM.  One JSON line per (shape, batch, fill, window, kind): median device time per
 call, the K/V (+ scale) bytes a call has to read, bytes per second and the run-to-run spread.
 
+`--kinds mxfp8+write,mxfp8+append --fills 256,32000 --windows 0` measures the quantizing append: the
+attention call that appends the new token's K / V rows itself (the APP form, `k_new=` ...) against
+`ops.kv_cache_write` followed by the same attention call, both on MXFP8 caches, the new rows being views of a
+QKV buffer as in the decode step.
+
 `--kinds bf16` runs the bf16 cache alone: it needs nothing of the MXFP8 interface, so the same file
 measures an older checkout (run it with that checkout as the working directory)."""
 import argparse
@@ -20,13 +25,13 @@ sys.path.insert(0, ".")
 import neuronx_distributed_llama3_2_amd.ops as ops  # noqa: E402
 
 SHAPES = [("32/8 D128", 32, 8, 128), ("llama3.2-1b 32/8 D64", 32, 8, 64)]
-FILLS = [(2048, 2304), (32000, 32768)]     # keys filled, cache length
+FILLS = [(256, 384), (2048, 2304), (32000, 32768)]     # keys filled, cache length
 ROTATE_BYTES = 512 << 20
 
 
 def layer_bytes(kind, B, Hkv, Lmax, D):
     per = 2 if kind == "bf16" else 1
-    return 2 * B * Hkv * Lmax * (D * per + (D // 32 if kind == "mxfp8" else 0))
+    return 2 * B * Hkv * Lmax * (D * per + (0 if kind == "bf16" else D // 32))
 
 
 def make_layers(kind, B, Hkv, Lmax, D, copies):
@@ -44,15 +49,24 @@ def make_layers(kind, B, Hkv, Lmax, D, copies):
     return out
 
 
-def capture(q, layers, seq, window, o, inner):
-    for kc, vc, kw in layers:
-        ops.decode_attention(q, kc, vc, seq, out=o, window=window, **kw)
+def call(kind, q, layer, seq, window, o, new):
+    """One decode-attention call of `kind` on a layer's caches; new = (k_new, v_new, positions) of the append kinds."""
+    kc, vc, kw = layer
+    if kind == "mxfp8+write":      # the two calls the append form replaces
+        ops.kv_cache_write(new[0], new[1], kc, vc, new[2], **kw)
+    elif kind == "mxfp8+append":
+        kw = dict(kw, k_new=new[0], v_new=new[1], positions=new[2])
+    ops.decode_attention(q, kc, vc, seq, out=o, window=window, **kw)
+
+
+def capture(kind, q, layers, seq, window, o, inner, new):
+    for layer in layers:
+        call(kind, q, layer, seq, window, o, new)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         for i in range(inner):
-            kc, vc, kw = layers[i % len(layers)]
-            ops.decode_attention(q, kc, vc, seq, out=o, window=window, **kw)
+            call(kind, q, layers[i % len(layers)], seq, window, o, new)
     g.replay()
     torch.cuda.synchronize()
     return g
@@ -86,17 +100,20 @@ def main():
     for name, Hq, Hkv, D in SHAPES:
         for B in (int(b) for b in a.batches.split(",")):
             for filled, Lmax in fills:
-                layers = {k: make_layers(k, B, Hkv, Lmax, D, max(2, -(-ROTATE_BYTES // layer_bytes(k, B, Hkv, Lmax, D))))
-                          for k in kinds}
+                layers = {k: make_layers(k.split("+")[0], B, Hkv, Lmax, D,
+                                         max(2, -(-ROTATE_BYTES // layer_bytes(k, B, Hkv, Lmax, D)))) for k in kinds}
                 torch.manual_seed(0)
-                q = torch.randn(B, 1, Hq, D, device="cuda", dtype=torch.bfloat16)
+                qkv = torch.randn(B, 1, Hq + 2 * Hkv, D, device="cuda", dtype=torch.bfloat16)
+                q = qkv[:, :, :Hq]
+                # the new token's rows go to the last filled position
+                new = (qkv[:, :, Hq:Hq + Hkv], qkv[:, :, Hq + Hkv:], torch.full((B,), filled - 1, device="cuda", dtype=torch.int32))
                 o = torch.empty_like(q)
                 seq = torch.full((B,), filled, device="cuda", dtype=torch.int32)
                 for window in (int(w) for w in a.windows.split(",")):
                     if window >= filled:
                         continue
                     inner = {k: 8 * len(layers[k]) for k in kinds}
-                    graphs = {k: capture(q, layers[k], seq, window or None, o, inner[k]) for k in kinds}
+                    graphs = {k: capture(k, q, layers[k], seq, window or None, o, inner[k], new) for k in kinds}
                     reps = {k: max(3, int(30000.0 / max(time_graph(graphs[k], 3), 1.0))) for k in kinds}
                     samples = {k: [] for k in kinds}
                     for _ in range(a.rounds):
