@@ -9,6 +9,7 @@
 #include "common.h"
 #include "decode_attn.h"
 #include "decode_fused_mx.h"
+#include "tree_attn.h"
 
 #include <execinfo.h>
 #include <csignal>
@@ -712,6 +713,69 @@ void decode_attn(at::Tensor q, at::Tensor kc, at::Tensor vc, c10::optional<at::T
   }
   check_rc(rc, what);
   nxd::decode_attn_set_prefetch(nullptr, 0, nullptr, 0, 0);   // armed ranges never outlive one call
+}
+
+// Tree-verification attention (csrc/tree_attn.hip): q / out [B, N, Hq, D]; k_tree / v_tree [B, N, Hkv, D]
+// (views of the QKV buffer); mask_words int64 [N], bit j of word n: node n sees tree key j; bf16 caches
+// [Bc, Hkv, Lmax, D]; prefix_len int32 [B] (device: the launch does not depend on its value).  Returns
+// false, nothing launched, for a well-formed call the kernel does not cover (the op then falls back).
+bool tree_attn(at::Tensor q, at::Tensor k_tree, at::Tensor v_tree, at::Tensor mask_words, at::Tensor kc, at::Tensor vc,
+               c10::optional<at::Tensor> cache_idx, at::Tensor prefix_len, at::Tensor out, double scale) {
+  int64_t qs[3], ks[3], vs[3], os[3];
+  bshd_strides(q, "q", qs);
+  bshd_strides(k_tree, "k_tree", ks);
+  bshd_strides(v_tree, "v_tree", vs);
+  bshd_strides(out, "out", os);
+  const int64_t B = q.size(0), N = q.size(1), Hq = q.size(2), D = q.size(3);
+  TORCH_CHECK(out.sizes() == q.sizes(), "tree_attn: out shape mismatch");
+  check_bf16(kc, "k_cache");
+  check_bf16(vc, "v_cache");
+  TORCH_CHECK(kc.dim() == 4 && vc.sizes() == kc.sizes() && vc.strides() == kc.strides() && kc.stride(3) == 1,
+              "tree_attn: caches must be [Bc, Hkv, Lmax, D] with unit stride on D and one layout");
+  for (int i = 0; i < 3; ++i) TORCH_CHECK(kc.stride(i) % 8 == 0 || kc.size(i) == 1, "tree_attn: cache strides must be multiples of 8 elements");
+  check_aligned16(kc, "k_cache");
+  check_aligned16(vc, "v_cache");
+  const int64_t Hkv = kc.size(1), Lmax = kc.size(2);
+  TORCH_CHECK(kc.size(3) == D, "tree_attn: head dim mismatch");
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "tree_attn: q heads must be a multiple of kv heads");
+  TORCH_CHECK(k_tree.sizes() == v_tree.sizes() && ks[0] == vs[0] && ks[1] == vs[1] && ks[2] == vs[2],
+              "tree_attn: k_tree / v_tree layouts must match");
+  TORCH_CHECK(k_tree.size(0) == B && k_tree.size(1) == N && k_tree.size(2) == Hkv && k_tree.size(3) == D,
+              "tree_attn: k_tree / v_tree must be [B, N, Hkv, D] of the call");
+  TORCH_CHECK(mask_words.scalar_type() == at::kLong && mask_words.dim() == 1 && mask_words.size(0) == N && mask_words.is_contiguous(),
+              "tree_attn: mask_words must be int64 [N]");
+  TORCH_CHECK(prefix_len.scalar_type() == at::kInt && prefix_len.dim() == 1 && prefix_len.size(0) == B && prefix_len.is_contiguous(),
+              "tree_attn: prefix_len must be int32 [B]");
+  for (const at::Tensor* t : {&k_tree, &v_tree, &mask_words, &kc, &vc, &prefix_len, &out})
+    TORCH_CHECK(t->device() == q.device(), "tree_attn: every tensor must be on q's device");
+  TORCH_CHECK(!cache_idx.has_value() || (cache_idx->device() == q.device() && cache_idx->is_contiguous()),
+              "tree_attn: cache_idx must be a contiguous tensor on q's device");
+  const int* rows = cache_rows(cache_idx, kc, B);
+  if (B > INT32_MAX || Hq > INT32_MAX || Lmax > INT32_MAX || kc.size(0) > INT32_MAX) return false;
+  const int nsplit = nxd::tree_attn_splits((int)B, (int)N, (int)Hq, (int)Hkv, (int)D, (int)Lmax);
+  if (nsplit < 0) return false;
+  nxd::TreeAttnArgs a{};
+  a.q = q.data_ptr(); a.q_sb = qs[0]; a.q_sn = qs[1]; a.q_sh = qs[2];
+  a.k_tree = k_tree.data_ptr(); a.v_tree = v_tree.data_ptr(); a.t_sb = ks[0]; a.t_sn = ks[1]; a.t_sh = ks[2];
+  a.mask_words = reinterpret_cast<const uint64_t*>(mask_words.data_ptr<int64_t>());
+  a.kc = kc.data_ptr(); a.vc = vc.data_ptr();
+  a.c_sb = kc.stride(0); a.c_sh = kc.stride(1); a.c_sl = kc.stride(2);
+  a.cache_idx = rows;
+  a.prefix_len = prefix_len.data_ptr<int>();
+  a.out = out.data_ptr(); a.o_sb = os[0]; a.o_sn = os[1]; a.o_sh = os[2];
+  a.B = B; a.N = N; a.Hq = Hq; a.Hkv = Hkv; a.D = D; a.Bc = kc.size(0); a.Lmax = Lmax;
+  a.scale = (float)scale;
+  a.stream = cur_stream();
+  at::Tensor part;   // [rows * D | rows | rows] fp32: po, pm, pl
+  if (nsplit > 1) {
+    const int64_t prow = B * Hkv * nsplit * (Hq / Hkv) * N;
+    part = at::empty({prow * (D + 2)}, q.options().dtype(at::kFloat));
+    a.po = part.data_ptr<float>(); a.pm = a.po + prow * D; a.pl = a.pm + prow;
+  }
+  const int rc = nxd::tree_attn_launch(a, nsplit);
+  if (rc == -1) return false;
+  check_rc(rc, "tree_attn");
+  return true;
 }
 
 // k, v: [B, T, Hkv, D] strided; caches [Bc, Hkv, Lmax, D]; pos: int32 [B] position of token 0
@@ -1652,6 +1716,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("decode_attn_set_sync", [](int64_t v) { nxd::decode_attn_set_sync((int)v); });
   m.def("decode_attn_set_oproj_maxl", [](int64_t v) { nxd::decode_attn_set_oproj_maxl((int)v); });
   m.def("decode_attn_prefetch", &decode_attn_prefetch);
+  m.def("tree_attn", &tree_attn, py::arg("q"), py::arg("k_tree"), py::arg("v_tree"), py::arg("mask_words"),
+        py::arg("k_cache"), py::arg("v_cache"), py::arg("cache_idx"), py::arg("prefix_len"), py::arg("out"), py::arg("scale"));
   m.def("kv_cache_write", &kv_cache_write, py::arg("k"), py::arg("v"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("cache_idx"), py::arg("pos"), py::arg("k_scale") = py::none(), py::arg("v_scale") = py::none());
   m.def("mx8_dequant", &mx8_dequant);

@@ -637,15 +637,19 @@ class DecoderInferenceMixin:
             raise NotImplementedError("tree verification reads a bf16 KV cache; kv_cache_dtype='mxfp8' is not supported")
         N = tokens.shape[0]
         nq, nkv, D = self.nq, self.nkv, self.head_dim
-        g = nq // nkv
         W = (nq + 2 * nkv) * D
         cos_t, sin_t = self.model.rope_cache.tables(tokens.device)
-        scale = 1.0 / math.sqrt(D)
         emb = self.model.embed_tokens
         x = self._all_reduce(ops.vocab_parallel_embedding(tokens.view(1, N), emb.weight, emb.start_index))
         residual = None
         kvs = []
-        tree_bias = torch.zeros((N, N), dtype=torch.float32, device=tokens.device).masked_fill(~tree_mask, float("-inf"))
+        # once per pass, not per layer, where the kernel runs: the mask words and the device prefix_len / cache row
+        # it reads.  Elsewhere both stay Python ints, which the op's fp32 arithmetic slices by without a host read.
+        plen, sid = prefix_len, [seq_id]
+        if tokens.is_cuda and ops.tree_attention_enabled() and N <= 64 and emb.weight.dtype == torch.bfloat16:
+            tree_mask = ops.pack_tree_mask(tree_mask)
+            plen = torch.full((1,), prefix_len, dtype=torch.int32, device=tokens.device)
+            sid = torch.full((1,), seq_id, dtype=torch.int32, device=tokens.device)
         for i, layer in enumerate(self.model.layers):
             attn = layer.self_attn
             h, residual = self._norm(x, layer.input_layernorm.weight, residual)
@@ -654,18 +658,9 @@ class DecoderInferenceMixin:
             qkv4 = qkv.view(N, nq + 2 * nkv, D)
             q, k, v = qkv4[:, :nq], qkv4[:, nq:nq + nkv], qkv4[:, nq + nkv:]
             kvs.append((k.clone(), v.clone()))
-            kc = self.kv_cache[i, 0, seq_id, :, :prefix_len].float()   # [Hkv, P, D]
-            vc = self.kv_cache[i, 1, seq_id, :, :prefix_len].float()
-            qf = q.float().permute(1, 0, 2).reshape(nkv, g * N, D)    # heads grouped by kv head
-            s_c = torch.matmul(qf, kc.transpose(1, 2)) * scale         # [Hkv, g*N, P]
-            s_t = torch.matmul(qf, k.float().permute(1, 2, 0)) * scale  # [Hkv, g*N, N]
-            s_t = s_t.view(nkv, g, N, N) + tree_bias
-            s = torch.cat([s_c.view(nkv, g, N, prefix_len), s_t], -1)
-            p_ = torch.softmax(s, -1)
-            o = torch.matmul(p_[..., :prefix_len].reshape(nkv, g * N, prefix_len), vc) + \
-                torch.matmul(p_[..., prefix_len:].reshape(nkv, g * N, N), v.float().permute(1, 0, 2))
-            o = o.view(nq, N, D).permute(1, 0, 2).reshape(1, N, nq * D).to(x.dtype)
-            x = self._row(attn.o_proj, o)
+            o = ops.tree_attention(q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), tree_mask, self.kv_cache[i, 0],
+                                   self.kv_cache[i, 1], plen, sid)
+            x = self._row(attn.o_proj, o.view(1, N, nq * D))
             h, residual = self._norm(x, layer.post_attention_layernorm.weight, residual)
             x = self._ffn(layer, h)
         h, _ = self._norm(x, self.model.norm.weight, residual)

@@ -41,11 +41,20 @@ Where the MFMA kernel covers the call ((Hq / Hkv) * T <= 16, head dim 64 or 128,
 `k_new` / `v_new` and quantizes it in registers, so nothing the launch writes is read in it.  Elsewhere
 (off the GPU, `NXD_FORCE_REFERENCE=1`, larger query groups, other head dims) it is the two calls.
 The fused decode step of an MXFP8-cache model uses it (inference/model_base.py, `NXD_DECODE_FUSED_KV8`).
+
+Tree verification (csrc/tree_attn.hip)
+--------------------------------------
+`tree_attention` is the attention of a Medusa verification pass: N <= 64 tree nodes whose K / V rows stay out
+of the cache attend over the cached prefix (a device `prefix_len`: static shapes) and over each other under a
+tree mask, packed by `pack_tree_mask` into one 64-bit word per node.  The kernel covers bf16, head dim 64 /
+128 and (Hq / Hkv) * N <= 512 query rows per kv head; elsewhere, and with `NXD_TREE_ATTN=0`, the fp32 PyTorch
+arithmetic in the function runs, which is also the CPU reference.  MXFP8 caches are refused (`TypeError`).
 """
 
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import torch
@@ -212,6 +221,94 @@ def kv_cache_write(k_new: torch.Tensor, v_new: torch.Tensor, k_cache: torch.Tens
         n = max(0, min(T, k_cache.shape[2] - p0))
         k_cache[cb, :, p0:p0 + n] = k_new[b, :n].transpose(0, 1).to(k_cache.dtype)
         v_cache[cb, :, p0:p0 + n] = v_new[b, :n].transpose(0, 1).to(v_cache.dtype)
+
+
+TREE_MAX_NODES = 64   # one 64-bit mask word per node
+
+
+def tree_attention_enabled() -> bool:
+    """The NXD_TREE_ATTN knob (default 1): 0 keeps `tree_attention` on its plain-PyTorch arithmetic."""
+    return os.environ.get("NXD_TREE_ATTN", "1") != "0"
+
+
+def pack_tree_mask(tree_mask: torch.Tensor) -> torch.Tensor:
+    """bool [N, N] (node i sees node j), N <= 64 -> int64 [N], bit j of word i."""
+    N = tree_mask.shape[0]
+    if tree_mask.dtype != torch.bool or tree_mask.dim() != 2 or tree_mask.shape[1] != N or N > TREE_MAX_NODES:
+        raise ValueError(f"tree_mask must be bool [N, N] with N <= {TREE_MAX_NODES}, got {tuple(tree_mask.shape)}")
+    bits = torch.arange(N, dtype=torch.int64, device=tree_mask.device)
+    return (tree_mask.to(torch.int64) << bits).sum(-1)
+
+
+def _rows16(*ts: torch.Tensor) -> bool:
+    """Unit inner stride, 16-byte aligned base and outer strides (8 bf16): what the 16-byte loads need."""
+    return all(t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and
+               all(s % 8 == 0 or n == 1 for s, n in zip(t.stride()[:-1], t.shape[:-1])) for t in ts)
+
+
+def tree_attention(q: torch.Tensor, k_tree: torch.Tensor, v_tree: torch.Tensor, tree_mask: torch.Tensor,
+                   k_cache: torch.Tensor, v_cache: torch.Tensor, prefix_len, cache_idx=None,
+                   softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Tree-verification attention (Medusa; csrc/tree_attn.hip).  q [B, N, Hq, D]: the queries of N tree
+    nodes; k_tree / v_tree [B, N, Hkv, D]: their keys / values, which are NOT in the cache.  Every node
+    sees the cached keys [0, prefix_len[b]) of cache row cache_idx[b] (caches [Bc, Hkv, Lmax, D]) and the
+    tree keys its mask row allows: tree_mask is bool [N, N] (node i sees node j) or the packed int64 [N]
+    of `pack_tree_mask`, shared by the batch.  prefix_len: int32 tensor [B], which the kernel reads on the
+    device (static shapes), or a Python int for every sequence; cache_idx: None (the identity), an int32
+    tensor [B] or a list of ints.  uint8 (MXFP8) caches raise TypeError.  Returns [B, N, Hq, D].
+
+    The kernel covers bf16 with D 64 / 128, N <= 64, (Hq / Hkv) * N <= 512 and 16-byte aligned rows (strides
+    of 8 elements).  Elsewhere -- off the GPU, NXD_FORCE_REFERENCE=1, NXD_TREE_ATTN=0, other shapes, dtypes
+    or layouts -- the plain-PyTorch fp32 arithmetic below runs.  It slices by the values of prefix_len and
+    cache_idx: given as tensors on the GPU that is a host read each, given as Python ints it is none.
+
+    Values are not checked on the kernel route (it runs inside hipGraphs): it clamps cache_idx[b] into
+    [0, Bc) and prefix_len[b] into [0, Lmax], as the decode kernels do, where the fp32 arithmetic would
+    raise IndexError or read a shorter slice.  A node that sees no key at all is zeros from the kernel and NaN
+    from that arithmetic; a tree mask has its diagonal set."""
+    B, N, Hq, D = q.shape
+    if k_cache.dtype == torch.uint8 or v_cache.dtype == torch.uint8:
+        raise TypeError("tree_attention reads a bf16 KV cache; uint8 (MXFP8) caches are not supported")
+    packed = tree_mask.dtype == torch.int64
+    if packed:
+        if tree_mask.shape != (N,) or N > TREE_MAX_NODES:
+            raise ValueError(f"a packed tree mask is int64 [N] with N <= {TREE_MAX_NODES}")
+    elif tree_mask.dtype != torch.bool or tree_mask.shape != (N, N):
+        raise ValueError("tree_mask must be bool [N, N] or packed int64 [N]")
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
+    if isinstance(prefix_len, int):
+        prefix_len = [prefix_len] * B
+    if out is None:
+        out = torch.empty((B, N, Hq, D), dtype=q.dtype, device=q.device)
+    ts = (q, k_tree, v_tree, k_cache, v_cache, out)
+    if (tree_attention_enabled() and N <= TREE_MAX_NODES and use_native(*ts) and all(t.dtype == torch.bfloat16 for t in ts)
+            and _rows16(*ts) and k_tree.stride() == v_tree.stride() and k_cache.stride() == v_cache.stride()):
+        words = tree_mask if packed else pack_tree_mask(tree_mask)
+        i32 = lambda x: torch.as_tensor(x, dtype=torch.int32, device=q.device).contiguous()  # noqa: E731
+        if ext().tree_attn(q, k_tree, v_tree, words.contiguous(), k_cache, v_cache,
+                           i32(cache_idx) if cache_idx is not None else None, i32(prefix_len), out, float(scale)):
+            return out
+    if packed:
+        tree_mask = ((tree_mask[:, None] >> torch.arange(N, dtype=torch.int64, device=tree_mask.device)) & 1).bool()
+    Hkv = k_cache.shape[1]
+    g = Hq // Hkv
+    tree_bias = torch.zeros((N, N), dtype=torch.float32, device=q.device).masked_fill(~tree_mask, float("-inf"))
+    for b in range(B):
+        cb = int(cache_idx[b]) if cache_idx is not None else b
+        P = int(prefix_len[b])
+        k, v = k_tree[b], v_tree[b]
+        kc = k_cache[cb, :, :P].float()   # [Hkv, P, D]
+        vc = v_cache[cb, :, :P].float()
+        qf = q[b].float().permute(1, 0, 2).reshape(Hkv, g * N, D)    # heads grouped by kv head
+        s_c = torch.matmul(qf, kc.transpose(1, 2)) * scale         # [Hkv, g*N, P]
+        s_t = torch.matmul(qf, k.float().permute(1, 2, 0)) * scale  # [Hkv, g*N, N]
+        s_t = s_t.view(Hkv, g, N, N) + tree_bias
+        s = torch.cat([s_c.view(Hkv, g, N, P), s_t], -1)
+        p_ = torch.softmax(s, -1)
+        o = torch.matmul(p_[..., :P].reshape(Hkv, g * N, P), vc) + \
+            torch.matmul(p_[..., P:].reshape(Hkv, g * N, N), v.float().permute(1, 0, 2))
+        out[b] = o.view(Hq, N, D).permute(1, 0, 2).to(out.dtype)
+    return out
 
 
 def argmax_rows(x: torch.Tensor) -> torch.Tensor:
